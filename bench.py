@@ -1,8 +1,23 @@
 #!/usr/bin/env python3
 """Benchmark: greedy adaptive-attention decode (Encoder2Decoder.sampler, max_len=20) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 512] [--max-len 20]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 512] [--max-len 20] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
+
+A plain run does what the headline figure needs and nothing else: it sets up (which includes
+SETTLE_STEPS untimed decodes, ~0.3 s: see the constant), runs W warm-up steps, times ONE region of exactly K sequential steps (``value`` = captions / that region's wall time,
+``ms_per_step`` = that time / K), writes the outputs if ``--dump-outputs`` is given and prints the
+line.  ``--full`` adds everything else described below (the eval loop, the pipelined region, >= 5
+regions per mode with the median reported, the per-kernel / roofline figures, the N > 1 cross-check,
+the CPU baseline); without it those fields are absent from the line and the options that shape them
+(``--regions``, ``--pipeline-depth``, ``--no-trace``, ``--no-eval-loop``, ``--no-cpu-baseline``,
+``--cpu-budget``) have nothing to act on.
+
+``--dump-outputs DIR`` writes what the last timed sequential step's ``sampler()`` call returned as
+``DIR/ids.npy`` (float64, exact for token ids), ``DIR/alpha.npy`` and ``DIR/beta.npy`` (float32); at
+most 64 MB in all (beyond that a fixed, seeded sample of rows, listed in ``DIR/<name>_rows.npy``).
+Inputs and weights are counter-based, so the same arguments give the same inputs in every run and
+two builds can be compared output for output.
 
 ``--gpus N`` with N > 1 and no torchrun environment (WORLD_SIZE unset) starts the N ranks itself:
 torch.distributed.run as a CHILD process (never an exec), before any GPU call, whose rank 0 prints
@@ -21,10 +36,10 @@ batch per call, filled by a device copy (the stand-in for ``to_var(images)``'s `
 ``model.sampler(images)`` and the ids to the host -- timed with events around the sampler call
 (``value``) and by wall clock including the fill.  The same K batches with several in flight
 (adaptive_amd.pipeline.DecodePipeline, one distinct feature batch per batch in flight) are reported
-in ``pipelined``.  Every mode is timed over >= 5 regions of exactly K steps and the median region is
-reported.  Rank 0 prints ONE JSON line.
+in ``pipelined``.  With ``--full`` every mode is timed over >= 5 regions of exactly K steps and the
+median region is reported.  Rank 0 prints ONE JSON line.
 
-Extra fields: ``roofline`` for the dominant kernel (per-launch algorithmic bytes or FLOPs / its
+Extra fields (``--full``): ``roofline`` for the dominant kernel (per-launch algorithmic bytes or FLOPs / its
 MEDIAN launch duration, from the dispatch's own begin / end timestamps: each traced launch gets a
 hipExtLaunchKernel start / stop event pair on its launch stream -- the timestamps rocprofv3's kernel
 trace reads, so the figure reproduces from the rocprofv3 summary of the same region committed under
@@ -391,6 +406,66 @@ def plumbing_main(args, world: int, rank: int) -> None:
     dist.destroy_process_group()
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: upper bound on the bytes written, all arrays together
+# Untimed decodes a plain run makes as part of its set-up, before the W warm-up steps.  A process's
+# decodes number ~50-200 run about 2 % slower than those before and after (3 warm-ups + 200 timed
+# steps: 463-467 K captions/s; 200 warm-ups + 200 timed: 471-480 K; 50 timed steps after 3, 50 or
+# 300 warm-ups: 472-481 K; profiles/plain_warmup_probe.txt), so a short --warmup would make the
+# figure depend on where the K timed steps fall; --full's regions start well past that point.
+SETTLE_STEPS = 300
+
+
+def dump_outputs(dirname: str, outputs: dict) -> None:
+    """``--dump-outputs``: write each tensor of ``outputs`` (what the last timed step's sampler() call
+    returned) as ``dirname/<name>.npy``: integer tensors as float64 (exact for token ids), the rest
+    as float32.  When the arrays together would exceed DUMP_BYTES, every array keeps the same
+    fraction of its rows, chosen by a fixed seed (sorted; the row numbers go to ``<name>_rows.npy``),
+    so two runs with the same arguments write the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: t.detach().cpu().numpy() for k, t in outputs.items()}
+    arrs = {k: a.astype(np.float32 if a.dtype.kind == "f" else np.float64) for k, a in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(a.shape[0] * 0.95 * DUMP_BYTES / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step written to {dirname}: " +
+        ", ".join(f"{k} {list(a.shape)}" for k, a in arrs.items()))
+
+
+def headline(args, world: int, backend: str, nbuf: int, value: float, ms_per_step: float) -> dict:
+    """The fields every line carries (plain or ``--full``): the metric, its value and the
+    configuration it was measured in."""
+    B, T = args.batch, args.max_len
+    return {
+        "metric": METRIC, "value": value, "unit": "captions/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "fp32", "full": bool(args.full),
+        "settle_steps": 0 if args.full else SETTLE_STEPS,
+        "data": "synthetic: counter-based U[0,1) post-trunk features [B,2048,7,7] and synthetic random-init "
+                "weights of the reference architecture (adaptive_amd/synth.py, seed 123)",
+        "config": {"workload": f"greedy decode (Encoder2Decoder.sampler) B={B}/GPU, max_len={T}",
+                   "batch_per_gpu": B, "global_batch": world * B, "max_len": T, "hidden": H, "embed": E,
+                   "vocab": V, "parallelism": f"dp{world}" + ("+allgather(ids)" if world > 1 else "")
+                   + ("" if backend == "nccl" else f" ({backend} rehearsal)"),
+                   "batches_in_flight": 1, "feature_buffers": nbuf,
+                   "launch": "direct kernel launches from one C call per sampler() (no hipGraph, no per-buffer cache)",
+                   "vocab_stage": "k_vscreen8 (bf16 screen, granule summaries) + exact fp32 rescoring of the "
+                                  "candidates inside the next step's k_lstm launch (k_vrescore for the last step)",
+                   "timed_step": "decode + (N > 1: all-gather of ids) + ids device->host copy",
+                   "headline": "one sampler() call after another on resident batches"},
+        "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        "backend": (dist.get_backend() if world > 1 else None),
+        # SURVEY.md §8d: the north star's "fraction of the HBM roofline" -- algorithmic bytes of one step
+        # (inputs + outputs + every weight once + the embedding rows touched) over the step time
+        "hbm_frac_path": path_bytes(B, T) * value / world / B / PEAK_HBM,
+        "path_bytes_per_batch": path_bytes(B, T),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -398,6 +473,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=512, help="images per GPU")
     ap.add_argument("--max-len", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: >= 5 regions per "
+                    "mode (median reported), the eval loop, the pipelined region, per-kernel / roofline figures, "
+                    "the N > 1 cross-check, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the ids / alpha / beta of the last "
+                    "timed sequential step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-trace", action="store_true", help="skip the per-kernel HIP events")
@@ -468,10 +548,34 @@ def main():
             ids = gather_rows(ids, world * B)
         if not args.no_d2h:
             host_ids[i & 1].copy_(ids, non_blocking=True)
+        return ids
 
     def step(i, trace=None):
         ids, alpha, beta = model.sampler(bufs[i % nbuf], max_len=T, trace=trace)
-        finish(i, ids)
+        return finish(i, ids), alpha, beta
+
+    K = args.steps
+    last = {}  # what the last timed sequential step returned (--dump-outputs)
+
+    def sequential(n, trace_list=None):
+        for k in range(n):
+            outs = step(k, trace_list[k][1] if trace_list else None)
+        if n and not trace_list:
+            last.update(zip(("ids", "alpha", "beta"), outs))
+
+    if not args.full:
+        # the plain run: settle, W warm-up steps, one timed region of exactly K steps, the line
+        sequential(SETTLE_STEPS)
+        sequential(args.warmup)
+        elapsed = time_region(lambda: sequential(K), world, torch.cuda.synchronize, dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)
+        if rank == 0:
+            print(json.dumps(headline(args, world, backend, nbuf, world * B * K / elapsed, 1e3 * elapsed / K)),
+                  flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     pipe = DecodePipeline(model, max_len=T, depth=depth, raw_streams=not args.pool_streams)
 
@@ -483,7 +587,6 @@ def main():
         for i, (ids, _, _) in enumerate(pipe.run(bufs[i % nbuf] for i in range(n))):
             finish(i, ids)
 
-    K = args.steps
     eval_ev = EventArray(2 * K)
     cur = torch.cuda.current_stream(dev)
 
@@ -526,8 +629,7 @@ def main():
             elif mode == "eval_loop":
                 eval_loop(K)
             else:
-                for k in range(K):
-                    step(k, trace_list[k][1] if trace_list else None)
+                sequential(K, trace_list)
         return time_region(run, world, torch.cuda.synchronize, dev)
 
     # Regions: `--regions` (>= 5) timed regions of exactly K steps each for the sequential sampler
@@ -538,6 +640,8 @@ def main():
     R = max(5, args.regions)
     seq_regions = [timed() for _ in range(R)]
     log(f"sequential regions (s): {seq_regions}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     eval_regions, eval_sampler_s = [], []
     if not args.no_eval_loop:
         for _ in range(R):
@@ -695,24 +799,8 @@ def main():
                               "PCIe transfer is outside the metric, DESIGN.md §7), ids to the host; `value` times the "
                               "sampler call + ids copy by timing-only events, `value_incl_fill` the whole loop by "
                               "wall clock"}
-    out = {
-        "metric": METRIC, "value": value, "unit": "captions/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic: counter-based U[0,1) post-trunk features [B,2048,7,7] and synthetic random-init "
-                "weights of the reference architecture (adaptive_amd/synth.py, seed 123)",
-        "config": {"workload": f"greedy decode (Encoder2Decoder.sampler) B={B}/GPU, max_len={T}",
-                   "batch_per_gpu": B, "global_batch": world * B, "max_len": T, "hidden": H, "embed": E,
-                   "vocab": V, "parallelism": f"dp{world}" + ("+allgather(ids)" if world > 1 else "")
-                   + ("" if backend == "nccl" else f" ({backend} rehearsal)"),
-                   "batches_in_flight": 1, "feature_buffers": nbuf,
-                   "launch": "direct kernel launches from one C call per sampler() (no hipGraph, no per-buffer cache)",
-                   "vocab_stage": "k_vscreen8 (bf16 screen, granule summaries) + exact fp32 rescoring of the "
-                                  "candidates inside the next step's k_lstm launch (k_vrescore for the last step)",
-                   "timed_step": "decode + (N > 1: all-gather of ids) + ids device->host copy",
-                   "headline": "one sampler() call after another on resident batches"},
-        "ranks_seen": dist.get_world_size() if world > 1 else 1,
-        "backend": (dist.get_backend() if world > 1 else None),
+    out = headline(args, world, backend, nbuf, value, ms_per_step)
+    out.update({
         "rank_devices": topo,
         "cross_check": xcheck,
         "regions": {"count": R, "sequential_captions_per_s": [captions / e for e in seq_regions],
@@ -723,11 +811,7 @@ def main():
                       "note": "the same K batches with `batches_in_flight` in flight through "
                               "adaptive_amd.pipeline.DecodePipeline (each batch its own resident features, "
                               "its ids copied to the host on its own stream); an API the reference does not call"},
-        # the north star's "fraction of the HBM roofline" -- algorithmic bytes of one step
-        # (inputs + outputs + every weight once + the embedding rows touched) over the step time
-        "hbm_frac_path": path_bytes(B, T) * per_gpu_rate / B / PEAK_HBM,
         "hbm_frac_path_pipelined": path_bytes(B, T) * per_gpu_rate_pipe / B / PEAK_HBM,
-        "path_bytes_per_batch": path_bytes(B, T),
         "path_traffic": path_traffic(B, T, args.traffic_json),
         # SURVEY.md §8d's binding figure: F = 415,361,744 FLOP per caption against the fp32 peak
         "fp32_binding": {"flops_per_caption": F, "achieved_tflops": F * per_gpu_rate / 1e12,
@@ -766,7 +850,7 @@ def main():
                            "run on the aux stream beside the VWv GEMM, so they may overlap) against ms_per_step; "
                            "the rest is launch boundaries and the ids copy",
         "cpu_baseline": None,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(feats.cpu(), T, args.cpu_budget)

@@ -3,6 +3,8 @@
 # usage: bash run_gpu.sh <step>...   steps: smoke tests testsall bench benchq prof pmc beamtests beambench beamprof
 set -u
 mkdir -p gpurun_out
+out=${OUT_DIR:-bench_out}  # where the bench steps write their line and their log
+mkdir -p "$out"
 ok_or_fail() {  # continue on 0 (pass) or 1 (test failures); stop on crashes/timeouts
   local rc=$1 name=$2
   echo "[$name] exit $rc"
@@ -14,8 +16,8 @@ for step in "$@"; do
     one) timeout -k 10 600 python -u -m pytest ${TESTS:-tests/test_gpu_configs.py} -m gpu -v --timeout 300 --timeout-method thread > gpurun_out/pytest_one.log 2>&1; ok_or_fail $? one; tail -30 gpurun_out/pytest_one.log ;;
     tests) timeout -k 10 900 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; ok_or_fail $? tests; tail -15 gpurun_out/pytest_gpu.log ;;
     testsall) timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; ok_or_fail $? tests; tail -25 gpurun_out/pytest_gpu.log ;;
-    bench) timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; ok_or_fail $? bench; cat gpurun_out/bench.json; tail -5 gpurun_out/bench.err ;;
-    benchq) timeout -k 10 600 python bench.py --no-cpu-baseline --steps 10 > gpurun_out/bench.json 2> gpurun_out/bench.err; ok_or_fail $? bench; cat gpurun_out/bench.json; tail -5 gpurun_out/bench.err ;;
+    bench) timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err; ok_or_fail $? bench; cat $out/bench.json; tail -5 $out/bench.err ;;
+    benchq) timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 10 > $out/bench.json 2> $out/bench.err; ok_or_fail $? bench; cat $out/bench.json; tail -5 $out/bench.err ;;
     lanes) for n in 1 2 3 4; do timeout -k 10 300 python bench.py --no-cpu-baseline --no-trace --lanes $n ${LANES_ARGS:-} > gpurun_out/bench_l$n.json 2>> gpurun_out/bench.err; ok_or_fail $? lanes$n; python -c "import json;d=json.load(open('gpurun_out/bench_l$n.json'));print('lanes $n', round(d['value']), 'captions/s', round(d['ms_per_step'],3),'ms')"; done ;;
     prof) cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
           timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python bench.py --no-cpu-baseline --no-trace --steps 10 > gpurun_out/prof.log 2>&1; ok_or_fail $? prof ;;

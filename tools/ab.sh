@@ -7,7 +7,7 @@ set -u
 mkdir -p gpurun_out
 for rep in 1 2; do
   for lib in $LIBS; do
-    AA_LIB_PATH=$PWD/$lib timeout -k 10 150 python bench.py --no-cpu-baseline "$@" \
+    AA_LIB_PATH=$PWD/$lib timeout -k 10 150 python bench.py --full --no-cpu-baseline "$@" \
       > gpurun_out/ab.json 2> gpurun_out/ab.err || { echo "bench failed for $lib"; tail -5 gpurun_out/ab.err; exit 1; }
     echo "rep$rep $(basename $lib) $(python -c "
 import json;d=json.load(open('gpurun_out/ab.json'))

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do
   for spec in "$@"; do
     IFS=: read -r label envs args <<< "$spec"
-    env ${LIB:+AA_LIB_PATH=$PWD/$LIB} $envs timeout -k 10 150 python bench.py --no-cpu-baseline --steps ${STEPS:-30} $args \
+    env ${LIB:+AA_LIB_PATH=$PWD/$LIB} $envs timeout -k 10 150 python bench.py --full --no-cpu-baseline --steps ${STEPS:-30} $args \
       > gpurun_out/abe.json 2> gpurun_out/abe.err || { echo "bench failed for $label"; tail -5 gpurun_out/abe.err; exit 1; }
     echo "rep$rep $label $(python -c "
 import json;d=json.load(open('gpurun_out/abe.json'))

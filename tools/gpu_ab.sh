@@ -8,7 +8,7 @@ mkdir -p $out
 for rep in 1 2; do
   for cfg in $CONFIGS; do
     IFS=: read -r tag lib flags <<< "$cfg"
-    AA_LIB_PATH=$PWD/$lib timeout -k 10 150 python bench.py --no-cpu-baseline --no-eval-loop --pipeline-depth 1 --steps 20 \
+    AA_LIB_PATH=$PWD/$lib timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-eval-loop --pipeline-depth 1 --steps 20 \
       --decode-flags ${flags:-0} > $out/ab_${tag}_$rep.json 2> $out/ab_${tag}_$rep.err \
       || { echo "bench failed: $tag"; tail -5 $out/ab_${tag}_$rep.err; exit 1; }
     python3 - $out/ab_${tag}_$rep.json ${tag}_$rep <<'PY'

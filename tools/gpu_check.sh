@@ -21,7 +21,7 @@ for s in $steps; do
            grep -E "FAILED|ERROR|passed|failed" $out/pytest_gpu.log | tail -15 ;;
     smoke) step smoke timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
            tail -1 $out/smoke.log ;;
-    bench) step bench timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err
+    bench) step bench timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err
            python3 -c "import json;d=json.load(open('$out/bench.json'));e=d.get('eval_loop') or {};r=d['roofline'];print('value', round(d['value']), 'eval', round(e.get('value',0)), round(e.get('frac_of_value',0),3), 'pipe', round(d['pipelined']['value']), 'roofline', r['kernel'], round(r['frac'],3), round(r['avg_launch_ms']*1e3,2), 'us', {k: round(v['avg_ms']*1e3,2) for k,v in d['kernels'].items()})" ;;
     prof)  step prof timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $out/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-eval-loop --pipeline-depth 1 --steps 20 > $out/prof.log 2>&1
            f=$(find $out/prof -name '*kernel_stats.csv' | head -1); head -14 "$f" | cut -c1-160 ;;
@@ -31,7 +31,7 @@ for s in $steps; do
            f=$(find $out/prof_train -name '*kernel_stats.csv' | head -1); head -12 "$f" | cut -c1-140 ;;
     ab) # A/B of an environment switch: AB_VAR=name (values 0 / 1), two interleaved rounds of short bench runs
            for r in 1 2; do for v in 0 1; do
-             env ${AB_VAR:-AA_ENC_REMAP}=$v timeout -k 10 300 python bench.py --no-cpu-baseline --no-eval-loop --steps 20 > $out/ab$v.$r.json 2>> $out/ab.err; rc=$?
+             env ${AB_VAR:-AA_ENC_REMAP}=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-eval-loop --steps 20 > $out/ab$v.$r.json 2>> $out/ab.err; rc=$?
              echo "[ab $v] exit $rc" >&3; [ $rc -eq 0 ] || exit $rc
              python3 -c "import json;d=json.load(open('$out/ab$v.$r.json'));k=d['kernels'];print('${AB_VAR:-AA_ENC_REMAP}=$v', round(d['value']), 'pipe', round(d['pipelined']['value']), {n: round(e['avg_ms']*1e3,2) for n,e in k.items()})"
            done; done ;;
@@ -43,7 +43,7 @@ for s in $steps; do
            done; done ;;
     pipe) # pipelined-rate probe: depth 2/3/4 x slot streams raw/aux
            for ps in x; do for d in 2 3 4; do
-             timeout -k 10 300 python bench.py --no-cpu-baseline --no-eval-loop --no-trace --steps 20 --pipeline-depth $d > $out/pipe_${ps}_$d.json 2>> $out/pipe.err; rc=$?
+             timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-eval-loop --no-trace --steps 20 --pipeline-depth $d > $out/pipe_${ps}_$d.json 2>> $out/pipe.err; rc=$?
              echo "[pipe $ps $d] exit $rc" >&3; [ $rc -eq 0 ] || exit $rc
              python3 -c "import json;d=json.load(open('$out/pipe_${ps}_$d.json'));print('streams $ps depth $d seq', round(d['value']), 'pipe', round(d['pipelined']['value']))"
            done; done ;;

@@ -17,7 +17,7 @@ step() {  # name, then the command; stop unless it passed (0) or only had test f
 step tests timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread -o cache_dir=/tmp/pc > $out/pytest_gpu.log 2>&1
 tail -3 $out/pytest_gpu.log
 step smoke timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
-step bench timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err
+step bench timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err
 step prof timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $out/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-trace --steps 10 > $out/prof.log 2>&1
 for p in fetch write mfma; do
   step pmc_$p bash tools/pmc.sh m_$tag $p

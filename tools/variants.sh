@@ -6,7 +6,7 @@ set -u
 mkdir -p gpurun_out
 for spec in "$@"; do
   label=${spec%%:*}
-  args=${spec#*:}
+  args="--full ${spec#*:}"  # the pipelined and per-kernel figures printed below need the full run
   timeout -k 10 180 python bench.py --no-cpu-baseline --steps ${STEPS:-30} $args > gpurun_out/var_$label.json 2> gpurun_out/var_$label.err \
     || { echo "variant $label failed"; tail -5 gpurun_out/var_$label.err; exit 1; }
   echo "$label $(python -c "
