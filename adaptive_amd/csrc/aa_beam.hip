@@ -177,16 +177,10 @@ __global__ __launch_bounds__(256) void k_gsumm(int R, int V, int Vp, const float
 // 64 x 64 tiles (3,840 workgroups at config 4, 200 VGPRs: two workgroups per CU) measured 0.187 ms per
 // launch against 0.212 ms for 128 x 64 tiles (1,920 workgroups, 384 registers: one wave per SIMD, the
 // LDS and barrier latencies exposed); beams bitwise unchanged (round 3, A/B on one box)
-#ifndef AA_VX_BM
-#define AA_VX_BM 64
-#endif
-constexpr int VX_BM = AA_VX_BM, VX_BN = 64;
-// AA_VEXACT_OCC 3: three workgroups per CU (168 VGPRs, 5 spilled): 0.205 -> 0.183 ms per launch, beam
+constexpr int VX_BM = 64, VX_BN = 64;
+// launch bound 3: three workgroups per CU (168 VGPRs, 5 spilled): 0.205 -> 0.183 ms per launch, beam
 // 89.4K -> 96.7K captions/s on one box, bit-identical (round 3 A/B)
-#ifndef AA_VEXACT_OCC
-#define AA_VEXACT_OCC 3
-#endif
-__global__ __launch_bounds__(256, AA_VEXACT_OCC) void k_vexact(int R, int H, int V, int Vp, const float* __restrict__ u,
+__global__ __launch_bounds__(256, 3) void k_vexact(int R, int H, int V, int Vp, const float* __restrict__ u,
                                                    const float* __restrict__ W, const float* __restrict__ bias,
                                                    float* __restrict__ logits, float2* __restrict__ gsum) {
   __shared__ __attribute__((aligned(16))) float lds[Tile<VX_BM, VX_BN>::LDS_FLOATS];
@@ -679,22 +673,16 @@ int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, 
       hipLaunchKernelGGL(k_beam_select3, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t, end_id < 0 ? -1 : end_id,
                          w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar);
     } else {
-#define AA_VB3(H_)                                                                                            \
-  if (wide)                                                                                                   \
-    AA_TLAUNCH(vocab_events, 2 * t, k_vbeam5<H_>, dim3(((R + 255) / 256) * (L.Vp / 256)), dim3(1024), 0, s, R, L.V, \
-               L.Vp, (const bf16x8*)w.u3, p.mlp_w3, p.mlp_b, w.logits, w.gsum);                                 \
-  else                                                                                                        \
-    AA_TLAUNCH(vocab_events, 2 * t, k_vbeam4<H_>, dim3(((R + 127) / 128) * (L.Vp / 128)), dim3(256), 0, s, R, L.V, \
-               L.Vp, (const bf16x8*)w.u3, p.mlp_w3, p.mlp_b, w.logits, w.gsum)
       // 256 x 256 tiles when the padded vocabulary is whole 256-column tiles (V = 10,123: 40 of them)
       const bool wide = L.Vp % 256 == 0;  // else 128 x 128 tiles (k_vbeam4)
-      switch (H) {
-        case 256: AA_VB3(256); break;
-        case 512: AA_VB3(512); break;
-        case 768: AA_VB3(768); break;
-        default: AA_VB3(1024); break;
-      }
-#undef AA_VB3
+      aa_for_hidden(H, [&](auto h) {
+        if (wide)
+          AA_TLAUNCH(vocab_events, 2 * t, k_vbeam5<h.value>, dim3(((R + 255) / 256) * (L.Vp / 256)), dim3(1024), 0, s,
+                     R, L.V, L.Vp, (const bf16x8*)w.u3, p.mlp_w3, p.mlp_b, w.logits, w.gsum);
+        else
+          AA_TLAUNCH(vocab_events, 2 * t, k_vbeam4<h.value>, dim3(((R + 127) / 128) * (L.Vp / 128)), dim3(256), 0, s,
+                     R, L.V, L.Vp, (const bf16x8*)w.u3, p.mlp_w3, p.mlp_b, w.logits, w.gsum);
+      });
       hipLaunchKernelGGL(k_beam_select3, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t, end_id < 0 ? -1 : end_id,
                          w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar);
     }

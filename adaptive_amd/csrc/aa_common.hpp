@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "adaptive_amd.h"
 #include "aa_gemm.hpp"
 
@@ -66,3 +68,15 @@ static inline int aa_launch_status() {
   return e == hipSuccess ? AA_OK : (int)e;
 }
 static inline bool aa_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// Host dispatch on the hidden size: calls f(std::integral_constant<int, H>{}) for the supported H
+// (256, 512, 768, 1024; check_model admits no other), so a launch names its kernel as k<h.value>.
+template <class F>
+static inline void aa_for_hidden(int H, F&& f) {
+  switch (H) {
+    case 256: f(std::integral_constant<int, 256>{}); break;
+    case 512: f(std::integral_constant<int, 512>{}); break;
+    case 768: f(std::integral_constant<int, 768>{}); break;
+    default: f(std::integral_constant<int, 1024>{}); break;
+  }
+}

@@ -36,31 +36,18 @@ namespace aa {
 
 // Write-through stores (agent-scope relaxed atomic stores = `global_store_* sc1`): the line leaves
 // for memory at once instead of sitting dirty in this XCD's L2 until the kernel-end writeback, which
-// the next launch waits for (MI355X_MICROARCH.md, boundary: + dirty bytes / 6 TB/s).  AA_WT selects
-// which kernel outputs take them: 1 = k_lstm's attention-projection partials, 2 = + k_lstm's h / c /
-// s / split-h, 3 = + k_atten5's u / bf16 u / norms and k_vscreen2's summaries, 4 = + k_enc_v4's V.
-#ifndef AA_WT
-#define AA_WT 2
-#endif
-struct U64x2 {
-  uint64_t a, b;
-};
-template <int LVL, class T>
+// the next launch waits for (MI355X_MICROARCH.md, boundary: + dirty bytes / 6 TB/s).  k_lstm's
+// outputs take them (the attention-projection partials, h / c / s / split-h); on k_atten5's u /
+// bf16 u / norms, the screen's summaries and k_enc_v4's V they measured slower.
+template <class T>
 __device__ __forceinline__ void st_wt(T* p, const T& v) {
-  if constexpr (AA_WT < LVL) {
-    *p = v;
-  } else if constexpr (sizeof(T) == 4) {
+  if constexpr (sizeof(T) == 4) {
     __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
-  } else if constexpr (sizeof(T) == 8) {
+  } else {
+    static_assert(sizeof(T) == 8, "4- or 8-byte stores");
     __hip_atomic_store(reinterpret_cast<uint64_t*>(p), __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    static_assert(sizeof(T) == 16, "4-, 8- or 16-byte stores");
-    const U64x2 w = __builtin_bit_cast(U64x2, v);
-    uint64_t* q = reinterpret_cast<uint64_t*>(p);
-    __hip_atomic_store(q, w.a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(q + 1, w.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -475,26 +462,16 @@ __global__ __launch_bounds__(256, 2) void k_enc_v3(const float* __restrict__ fea
 // LDS as [image][channel][p], and one wave per stage (rotating) sums every channel of both images
 // sequentially in p order and divides by 49 -- k_avgpool's arithmetic, bit-identical to ATen.
 // ---------------------------------------------------------------------------------------------
-// The feature map is read once per batch: non-temporal loads (AA_FEAT_NT=1) keep the 205 MB stream from
+// The feature map is read once per batch: non-temporal loads keep the 205 MB stream from
 // evicting the step kernels' working set (V, W_m, the token table) of the batches in flight.
-#ifndef AA_FEAT_NT
-#define AA_FEAT_NT 1
-#endif
-#if AA_FEAT_NT
-#define AA_FEAT_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define AA_FEAT_LOAD(p) (*(p))
-#endif
 constexpr int E4_ROWS = 98, E4_RB = 7, E4_LD = 48;  // rows per workgroup, 16-row blocks, LDS pitch (bf16)
 constexpr int E4_SP = 52, E4_MAXC = 2048;           // a_g staging pitch (floats), largest channel count
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // NW waves (8 or 16): each wave owns NCB 16-column blocks (H = 16 NCB NW); the A staging is done by
 // the first 512 threads either way.  NW = 16 (four waves per SIMD instead of two, half the columns
-// each; the default at H = 512): k_enc_v4 247 -> 242 us, sequential decode +0.9 % (A/B, two rounds)
-#ifndef AA_ENC4_NW
-#define AA_ENC4_NW 16
-#endif
+// each; what H = 512 launches): k_enc_v4 247 -> 242 us, sequential decode +0.9 % (A/B, two rounds)
+constexpr int ENC4_NW = 16;
 
 template <int NCB, int NW = 8>
 __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ feats, int B, int C,
@@ -537,7 +514,7 @@ __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ fe
   auto gload_a = [&](int s) {
     const float* src = arow + (int64_t)(32 * s) * P;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ra[i] = AA_FEAT_LOAD(src + i * P);
+    for (int i = 0; i < 8; ++i) ra[i] = __builtin_nontemporal_load(src + i * P);
   };
   auto gload_w = [&](int s, int c) {
 #pragma unroll
@@ -657,7 +634,7 @@ __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ fe
     for (int q = t; q < F4; q += NT) {
       const int r = q / (H / 4), c4 = q % (H / 4), tr = rb * 16 + r, row = m0 + tr;
       if (tr < E4_ROWS && row < M)
-        st_wt<4>(reinterpret_cast<float4*>(V + (int64_t)row * H + 4 * c4), *reinterpret_cast<const float4*>(Vs + r * VSP + 4 * c4));
+        *reinterpret_cast<float4*>(V + (int64_t)row * H + 4 * c4) = *reinterpret_cast<const float4*>(Vs + r * VSP + 4 * c4);
     }
   }
 }
@@ -866,15 +843,12 @@ __global__ __launch_bounds__(256) void k_gemm_bias(const float* __restrict__ A, 
 // (Atten.affine_g / affine_s, adaptive_attention.py:35,45): part[b][tile][j] = sum_{u in tile}
 // (j < 49 ? h'_u W_g[j][u] : s_u W_s[j-49][u]); k_atten adds the H/16 partials in tile order.
 // ---------------------------------------------------------------------------------------------
-constexpr int PART = 128;  // partial-projection row pitch (AA_PART_ALIGN: W_g h outputs at 0..48, W_s s at 64..112)
-// Column of projection output j (0..97: W_g then W_s) in a partial row.  AA_PART_ALIGN: each half
+constexpr int PART = 128;  // partial-projection row pitch (W_g h outputs at 0..48, W_s s at 64..112)
+// Column of projection output j (0..97: W_g then W_s) in a partial row.  Each half
 // starts on a 256-B boundary, so every store instruction of the tile's projection phase (a 32 x 32
 // accumulator block: two rows x 32 columns) writes two whole 128-B lines (the write-through stores of
 // partial lines otherwise cost the memory side a read-modify-write each).
-#ifndef AA_PART_ALIGN
-#define AA_PART_ALIGN 1
-#endif
-__device__ __forceinline__ int part_col(int j) { return AA_PART_ALIGN ? (j < P ? j : 64 + (j - P)) : j; }
+__device__ __forceinline__ int part_col(int j) { return j < P ? j : 64 + (j - P); }
 
 // The GEMM h_{t-1} W_hh^T runs on bf16 MFMA with 3-way split operands (see k_enc_v3): h arrives
 // already split (hsp_in, written by the previous step's epilogue or k_split_rows) and W_hh is
@@ -955,9 +929,9 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
     Ss[u0 * HP + rr] = sn[0];
     Ss[(u0 + 1) * HP + rr] = sn[1];
     if (m < B) {
-      st_wt<2>(reinterpret_cast<float2*>(c_out + (int64_t)m * H + j), make_float2(cn[0], cn[1]));
-      st_wt<2>(reinterpret_cast<float2*>(h_out + (int64_t)m * H + j), make_float2(hn[0], hn[1]));
-      st_wt<2>(reinterpret_cast<float2*>(s_out + (int64_t)m * H + j), make_float2(sn[0], sn[1]));
+      st_wt(reinterpret_cast<float2*>(c_out + (int64_t)m * H + j), make_float2(cn[0], cn[1]));
+      st_wt(reinterpret_cast<float2*>(h_out + (int64_t)m * H + j), make_float2(hn[0], hn[1]));
+      st_wt(reinterpret_cast<float2*>(s_out + (int64_t)m * H + j), make_float2(sn[0], sn[1]));
       if (hsp_out) {
         // next step's A fragments: k = j.. in chunk nt, lane (m % 32) + 32 * (u0 / 8), elements u0 % 8..
         typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -970,9 +944,9 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
         }
         bf16x8* o = hsp_out + ((size_t)((m >> 5) * KC + nt) * 3) * 64 + (m & 31) + 32 * (u0 >> 3);
         const int e = u0 & 7;
-        st_wt<2>(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o) + e), p0);
-        st_wt<2>(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o + 64) + e), p1);
-        st_wt<2>(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o + 128) + e), p2);
+        st_wt(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o) + e), p0);
+        st_wt(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o + 64) + e), p1);
+        st_wt(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o + 128) + e), p2);
       }
     }
   }
@@ -993,15 +967,12 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
       const float wv = jj < P ? Wsl[u * WSP + jgc] : 0.f;
       pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wv, pacc, 0, 0, 0);
     }
-    // (AA_PART_ALIGN: all 32 lanes store -- columns jj >= P hold zeros, their W values being 0 -- so the
-    // lines are whole)
-    const int col = AA_PART_ALIGN ? (cb < 2 ? 0 : 64) + jj : jg;
-    if (AA_PART_ALIGN || jj < P) {
+    // (all 32 lanes store -- columns jj >= P hold zeros, their W values being 0 -- so the lines are whole)
+    const int col = (cb < 2 ? 0 : 64) + jj;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int mr = m0 + rb * 32 + acc_row(r, lane);
-        if (mr < B) st_wt<1>(&part[((int64_t)mr * NTn + nt) * PART + col], pacc[r]);
-      }
+    for (int r = 0; r < 16; ++r) {
+      const int mr = m0 + rb * 32 + acc_row(r, lane);
+      if (mr < B) st_wt(&part[((int64_t)mr * NTn + nt) * PART + col], pacc[r]);
     }
   }
 }
@@ -1018,18 +989,10 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
 // the DMAs).  `pre` runs after the first three stages are issued: it may issue exactly LS_GATHERS
 // ordinary loads (the cell's gathers), which the counted waits of the first two iterations account
 // for.  Ends with the K halves summed into Pt [column][row] (Pt aliases the ring).
-#ifndef AA_LSTM_NB
-#define AA_LSTM_NB 3
-#endif
-constexpr int LS_NB = AA_LSTM_NB;             // ring stages (LS_NB - 1 in flight ahead of the one multiplied)
+constexpr int LS_NB = 3;                      // ring stages (LS_NB - 1 in flight ahead of the one multiplied)
 constexpr int LS_STAGE = 24 * 64;             // bf16x8 per stage
 constexpr int LS_GATHERS = 12;                // ordinary loads issued by k_lstm's gathers (ISA-checked)
-// fragments each wave DMAs per ring stage (3; AA_RING_NPW = 2 is a timing-only probe that moves two
-// thirds of the bytes and computes garbage)
-#ifndef AA_RING_NPW
-#define AA_RING_NPW 3
-#endif
-constexpr int LS_NPW = AA_RING_NPW;
+constexpr int LS_NPW = 3;                     // fragments each wave DMAs per ring stage
 
 // s_waitcnt vmcnt(n) for an n that is a compile-time constant once the caller's loop is unrolled
 template <int V>
@@ -1158,9 +1121,6 @@ __device__ __forceinline__ void lstm_gemm_lds(const bf16x8* af0, const bf16x8* a
 // G (beam search): row m continues the hypothesis of row par[m] of the previous step, so its h
 // fragments and c are gathered from that row (the beams of an image are adjacent rows, so the
 // gathered 16-B fragment loads stay within the same or the neighbouring 32-row block).
-#ifndef AA_LSTM_OCC
-#define AA_LSTM_OCC 4
-#endif
 // The previous step's rescoring, run inside k_lstm<H, false, true> (greedy steps t >= 1): workgroups
 // 0 .. NR-1 rescore rows 2 bid, 2 bid + 1 of step t - 1 (k_vrescore's body, two 256-thread groups)
 // and publish each row's argmax key as one agent-scope 8-byte store into keys[t-1] (zeroed before
@@ -1188,14 +1148,9 @@ __device__ __forceinline__ uint64_t rescore_row(int b, bool write, int t, int V,
                                                 int64_t* __restrict__ ids, int T, int t_step, float* scr);
 constexpr uint64_t RS_WAIT_TICKS = 5000;  // 50 us of the 100 MHz constant clock
 // ring iterations (of H / 32) at which k_lstm<.., RS> DMAs the tile's keys and gathers the table rows
-#ifndef LS_RS_JK
-#define LS_RS_JK 10
-#endif
-#ifndef LS_RS_JG
-#define LS_RS_JG (LS_RS_JK + 3)
-#endif
+constexpr int LS_RS_JK = 10, LS_RS_JG = LS_RS_JK + 3;
 template <int H, bool G = false, bool RS = false>
-__global__ __launch_bounds__(512, AA_LSTM_OCC) void k_lstm(int B, int V, const int64_t* __restrict__ tok, int tok_ld,
+__global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __restrict__ tok, int tok_ld,
                                               const float* __restrict__ table,
                                               const float* __restrict__ xg, const bf16x8* __restrict__ hsp_in,
                                               const float* __restrict__ c_in, const int* __restrict__ par,
@@ -1584,7 +1539,6 @@ __global__ __launch_bounds__(256) void k_atten(int B, int NTL, int kdiv, const f
 // grp, grp + 4, ...); score item k = t >> 3, lane q = t & 7 (vwr / whr: its 7 terms j = q + 8 i);
 // context dimensions t + 512 i (hv, sv; V through vget(i, kk)).  The 32 projection partials are summed
 // by the four groups, then (g0 + g1) + (g2 + g3); each of the 50 scores by 8 lanes, xor-butterfly.
-// LVL: the st_wt level of the u / norm stores.
 struct AttSmem {
   float red[4][128];
   float proj[PART];
@@ -1593,7 +1547,7 @@ struct AttSmem {
   float norm[16];
   float beta;
 };
-template <int H, int LVL, class VG>
+template <int H, class VG>
 __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H / 64], const float (&vwr)[7],
                                                const float (&whr)[7], const float (&hv)[H / 512],
                                                const float (&sv)[H / 512], VG&& vget, AttSmem& sm,
@@ -1667,7 +1621,7 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
     const float chat = __builtin_fmaf(beta, sv[i], (1.f - beta) * c);
     const float u = chat + hv[i];
     nsq = __builtin_fmaf(u, u, nsq);
-    st_wt<LVL>(&u_out[(int64_t)b * H + d], u);
+    u_out[(int64_t)b * H + d] = u;
     if (ub_out) {
       const uint16_t ubv = f2bf(u);
       ub_out[frag_off(b, d, H)] = ubv;  // (2-byte: plain)
@@ -1691,9 +1645,11 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
     __syncthreads();
     if (t == 0) {
       const float* n = sm.norm;
-      st_wt<LVL>(&unorm[b], sqrtf(((n[0] + n[1]) + (n[2] + n[3])) + ((n[4] + n[5]) + (n[6] + n[7]))) * 1.0001f);
-      st_wt<LVL>(&unorm[B + b],
-                 sqrtf(((n[8] + n[9]) + (n[10] + n[11])) + ((n[12] + n[13]) + (n[14] + n[15]))) * 1.0001f);
+      // (each address is formed before its value: the instruction order the kernel was measured with)
+      float* const pu = &unorm[b];
+      *pu = sqrtf(((n[0] + n[1]) + (n[2] + n[3])) + ((n[4] + n[5]) + (n[6] + n[7]))) * 1.0001f;
+      float* const pd = &unorm[B + b];
+      *pd = sqrtf(((n[8] + n[9]) + (n[10] + n[11])) + ((n[12] + n[13]) + (n[14] + n[15]))) * 1.0001f;
     }
   }
   AA_TS(1, 4);
@@ -1738,30 +1694,19 @@ __global__ __launch_bounds__(512) void k_atten5(int B, int kdiv, const float* __
   }
   const float* vb = Vf + (int64_t)img * P * H;
   float vv[DPT][P];
-  // AA_ATTEN_VA: V rows issued before the small operands above are waited for; the rest of V is issued
-  // once they have landed, so the score chain's loads do not queue behind the whole V stream
-#ifndef AA_ATTEN_VA
-#define AA_ATTEN_VA P
-#endif
-  constexpr int VA = AA_ATTEN_VA < P ? AA_ATTEN_VA : P;
+  // all of V is issued before the small operands above are waited for (holding part of it back until
+  // they had landed measured no better)
 #pragma unroll
   for (int i = 0; i < DPT; ++i)
 #pragma unroll
-    for (int kk = 0; kk < VA; ++kk) vv[i][kk] = vb[(int64_t)kk * H + t + 512 * i];
-  if constexpr (VA < P) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VA * DPT) : "memory");
-#pragma unroll
-    for (int i = 0; i < DPT; ++i)
-#pragma unroll
-      for (int kk = VA; kk < P; ++kk) vv[i][kk] = vb[(int64_t)kk * H + t + 512 * i];
-  }
+    for (int kk = 0; kk < P; ++kk) vv[i][kk] = vb[(int64_t)kk * H + t + 512 * i];
   float hv[DPT], sv[DPT];
 #pragma unroll
   for (int i = 0; i < DPT; ++i) {
     hv[i] = h_new[(int64_t)b * H + t + 512 * i];
     sv[i] = s_new[(int64_t)b * H + t + 512 * i];
   }
-  atten_row_math<H, 3>(B, b, pv, vwr, whr, hv, sv, [&](int i, int kk) { return vv[i][kk]; }, sm, alpha_out, alpha_ld,
+  atten_row_math<H>(B, b, pv, vwr, whr, hv, sv, [&](int i, int kk) { return vv[i][kk]; }, sm, alpha_out, alpha_ld,
                        beta_out, beta_ld, u_out, ub_out, unorm, ub3_out);
 }
 
@@ -1956,9 +1901,6 @@ __device__ __forceinline__ void screen_bfly(uint32_t (&k1)[16], uint32_t (&k2)[1
   }
 }
 
-// Screen tile: 128 rows x 128 columns per workgroup, K in 64-wide bf16 steps staged through
-// double-buffered LDS (global->register prefetch of step k+1 under the MFMAs of step k); each
-// wave owns 64 x 64 = 2 x 2 blocks of v_mfma_f32_32x32x16_bf16.
 // Screen tile: 64 rows x 64 columns per 256-thread workgroup.  Both operands are bf16 in
 // MFMA-fragment order (u written so by k_atten, W_m at pack time), so wave w loads every fragment
 // of its quarter of K -- 2 x 2 blocks x H/64 chunks -- straight into VGPRs in one round trip,
@@ -2107,49 +2049,14 @@ __global__ __launch_bounds__(256, 2) void k_vscreen(int B, int V, int Vp, const 
 constexpr int SC2_BM = 128, SC2_NB = 5, SC2_BN = 32 * SC2_NB, SC2_KS = 4;
 constexpr int SC2_STAGE = SC2_NB * SC2_KS * 64;  // bf16x8 per LDS stage (20 KB)
 
-// Per (row, granule) summary of one 32 x 32 block of screened logits in MFMA C layout (rows row0..,
-// columns 32 G..): keys, transposing top-2 butterfly, bound E, one float4 per row (see k_vscreen).
-template <int H>
-__device__ __forceinline__ void screen_block_summ(const floatx16& blk, int row0, int G, float bv, float4 gsv,
-                                                  const float2* __restrict__ un_blk, bool valid, int B, int NTn,
-                                                  float4* __restrict__ summ) {
-  const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
-  uint32_t k1[16], k2[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const uint32_t key = order_key(blk[r] + bv);
-    k1[r] = valid ? (key & ~31u) | (uint32_t)li : 0u;
-    k2[r] = 0u;
-  }
-  screen_bfly<16>(k1, k2, li);
-  screen_bfly<8>(k1, k2, li);
-  screen_bfly<4>(k1, k2, li);
-  screen_bfly<2>(k1, k2, li);
-  const uint32_t r1 = partner<1>(k1[0]), r2 = partner<1>(k2[0]);
-  const uint32_t m1 = k1[0] > r1 ? k1[0] : r1;
-  const uint32_t lo = k1[0] > r1 ? r1 : k1[0], h2 = k2[0] > r2 ? k2[0] : r2;
-  const uint32_t m2 = lo > h2 ? lo : h2;
-  const int rr = (li >> 1) & 15;  // this lane pair now holds row acc_row(rr) of the block
-  const int rl = (rr & 3) + 8 * (rr >> 2) + 4 * lh;
-  const int row = row0 + rl;
-  if (!(li & 1) && row < B) {
-    float4 o = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
-    if (m1) {
-      const float E = screen_bound<H>(un_blk[rl], gsv);
-      const float x1 = key_value(m1 & ~31u);
-      const float x2 = m2 ? key_value(m2 & ~31u) : -INFINITY;
-      o = make_float4(x1 - E, x1 + E, x2 + E, __int_as_float(G * VS_TILE + (int)(m1 & 31u)));
-    }
-    summ[(int64_t)row * NTn + G] = o;
-  }
-}
-
-// screen_block_summ over a wave's NB column blocks at once, each butterfly level issued for every
-// block before the next level starts: with one wave per SIMD (k_vscreen2's grid is one workgroup
-// per CU) the late levels of one block (1 or 2 independent merges) leave the SIMD waiting on DPP and
-// VALU latency; NB blocks side by side give each level NB times the independent work.  The top-2
-// merge is max / med3: the second largest of {m1 >= m2, r1 >= r2} is med3(m1, r1, max(m2, r2)).
-// Same keys, same summaries as screen_block_summ per block.
+// Per (row, granule) summaries of a wave's NB 32 x 32 blocks of screened logits in MFMA C layout (rows
+// row0.., columns c0..): keys, transposing top-2 butterfly, bound E, one float4 per row and granule
+// (see k_vscreen's epilogue).  Each butterfly level is issued for every block before the next level
+// starts: with one wave per SIMD (k_vscreen2's grid is one workgroup per CU) the late levels of one
+// block (1 or 2 independent merges) leave the SIMD waiting on DPP and VALU latency; NB blocks side by
+// side give each level NB times the independent work.  The top-2 merge is max / med3: the second
+// largest of {m1 >= m2, r1 >= r2} is med3(m1, r1, max(m2, r2)).  Same keys, same summaries as
+// k_vscreen's epilogue gives per block.
 // median of three (the compiler emits v_med3_u32 for this pattern)
 __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) {
   const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
@@ -2226,55 +2133,59 @@ __device__ __forceinline__ void screen_blocks_summ(const floatx16 (&acc)[NB], in
         const float x2 = m2 ? key_value(m2 & ~31u) : -INFINITY;
         o = make_float4(x1 - E, x1 + E, x2 + E, __int_as_float((G0 + b) * VS_TILE + (int)(m1 & 31u)));
       }
-      st_wt<3>(&summ[(int64_t)row * NTn + G0 + b], o);
+      summ[(int64_t)row * NTn + G0 + b] = o;
     }
   }
 }
 
-// Main loop of the wide screen (k_vscreen2): the tile's screened products
-// acc[b] = bf16(u) . bf16(w) of wave w's 32 rows x column block b (no bias), and un_s = ||u|| of the
-// tile's 128 rows.
-template <int H>
-__device__ __forceinline__ void screen2_main(int B, int m0, int n0, const bf16x8* __restrict__ ua,
-                                             const float* __restrict__ unorm, const bf16x8* __restrict__ wf,
-                                             bf16x8 (*Ws)[SC2_STAGE], float2* un_s, floatx16 (&acc)[SC2_NB],
-                                             const float4* __restrict__ gs = nullptr, float4* gs_s = nullptr) {
-  constexpr int KC = H / 16, NS = KC / SC2_KS, PER = SC2_STAGE / 256;  // bf16x8 per thread per stage
+// Main loop of the wide screen on NT threads: the tile's screened products acc[b] = bf16(u) . bf16(w) of
+// the wave's 32 rows (row block wave & 3) x column blocks b0 .. b0 + NBW - 1 (no bias), and, staged in
+// LDS for the epilogue, un_s = ||u|| of the tile's 128 rows and gs_s = the 5 granules' bound factors
+// (no global loads inside the epilogue, no registers held across the loop).
+template <int H, int NT, int NBW, bool RING3>
+__device__ __forceinline__ void screen_main(int B, int m0, int n0, int b0, const bf16x8* __restrict__ ua,
+                                            const float* __restrict__ unorm, const bf16x8* __restrict__ wf,
+                                            bf16x8 (*Ws)[SC2_STAGE], float2* un_s, floatx16 (&acc)[NBW],
+                                            const float4* __restrict__ gs, float4* gs_s) {
+  constexpr int KC = H / 16, NS = KC / SC2_KS, PER = (SC2_STAGE + NT - 1) / NT;  // bf16x8 per thread per stage
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  // this wave's u fragments (row block m0 / 32 + wave) and the W stages arrive AA_SCREEN_AHEAD stages
-  // ahead in register rings instead of all KC chunks at once, so the kernel fits in 256 registers and
-  // 40 KB of LDS.  Two stages ahead (the default) hide more of the L2 latency than one (k_vscreen2
-  // 16.4 -> 15.5 us in A/B); three cost more in registers than they hide.
-  const bf16x8* a0 = ua + (size_t)((m0 >> 5) + wave) * KC * 64 + lane;
-#ifndef AA_SCREEN_AHEAD
-#define AA_SCREEN_AHEAD 2
-#endif
+  // this wave's u fragments and the W stages arrive two stages ahead in register rings instead of all
+  // KC chunks at once, so the kernel fits in 256 registers and 40 KB of LDS.  Two stages ahead hide
+  // more of the L2 latency than one (k_vscreen2 16.4 -> 15.5 us in A/B); three cost more in registers
+  // than they hide.
+  const bf16x8* a0 = ua + (size_t)((m0 >> 5) + (wave & 3)) * KC * 64 + lane;
   // stages in flight ahead of the one multiplied: W in registers (RW slots), u fragments (RU slots)
-  constexpr int AH = AA_SCREEN_AHEAD < NS ? AA_SCREEN_AHEAD : NS, RW = AH, RU = AH + 1;
+  constexpr int AH = 2 < NS ? 2 : NS, RW = AH, RU = AH + 1;
   bf16x8 fa[RU][SC2_KS];
   auto uload = [&](int s, int slot) {
 #pragma unroll
     for (int c = 0; c < SC2_KS; ++c) fa[slot][c] = a0[(size_t)(s * SC2_KS + c) * 64];
   };
   // W stage s: for column block b (0..4), chunks [s KS, (s+1) KS) are one contiguous 8 KB run of the
-  // fragment-order W_m; thread t moves bf16x8 j = t + 256 i of the stage (b = j / (KS*64)).
+  // fragment-order W_m; thread t moves bf16x8 j = t + NT i of the stage (b = j / (KS*64)).
   const bf16x8* wbase = wf + (size_t)(n0 >> 5) * KC * 64;
   bf16x8 wr[RW][PER];
   auto gload = [&](int s, int slot) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int j = t + 256 * i, b = j / (SC2_KS * 64), r = j - b * (SC2_KS * 64);
-      wr[slot][i] = wbase[((size_t)b * KC + s * SC2_KS) * 64 + r];
+      const int j = t + NT * i;
+      if (PER * NT == SC2_STAGE || j < SC2_STAGE) {  // (wave-uniform)
+        const int b = j / (SC2_KS * 64), r = j - b * (SC2_KS * 64);
+        wr[slot][i] = wbase[((size_t)b * KC + s * SC2_KS) * 64 + r];
+      }
     }
   };
   auto lstore = [&](int buf, int slot) {
 #pragma unroll
-    for (int i = 0; i < PER; ++i) Ws[buf][t + 256 * i] = wr[slot][i];
+    for (int i = 0; i < PER; ++i) {
+      const int j = t + NT * i;
+      if (PER * NT == SC2_STAGE || j < SC2_STAGE) Ws[buf][j] = wr[slot][i];
+    }
   };
 #pragma unroll
   for (int s = 0; s < AH; ++s) uload(s, s);
 #pragma unroll
-  for (int b = 0; b < SC2_NB; ++b)
+  for (int b = 0; b < NBW; ++b)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 #pragma unroll
@@ -2284,34 +2195,58 @@ __device__ __forceinline__ void screen2_main(int B, int m0, int n0, const bf16x8
   if (t < SC2_BM) {
     const int r = m0 + t;
     un_s[t] = make_float2(unorm[r < B ? r : B - 1], unorm[B + (r < B ? r : B - 1)]);
-  } else if (gs_s && t < SC2_BM + SC2_NB) {  // the granule bound factors, staged with ||u||
+  } else if (t < SC2_BM + SC2_NB) {
     gs_s[t - SC2_BM] = gs[n0 / VS_TILE + t - SC2_BM];
   }
+  if constexpr (RING3) {
+    // three LDS buffers: stage s + 1's W is stored in the middle of stage s's MFMAs (its
+    // buffer was last read in stage s - 2, before this stage's barrier), so the store's latency is off
+    // the barrier -> read -> MFMA path; one barrier per stage.  10.1 -> 9.7 us, sequential decode
+    // +0.7 % (A/B, profiles/r06i_screen_ring3_ab.txt); four stages ahead of the W / u loads: no gain
+    lstore(0, 0);
 #pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    lstore(s & 1, s % RW);
-    if (s + AH < NS) {
-      gload(s + AH, s % RW);
-      uload(s + AH, (s + AH) % RU);
+    for (int s = 0; s < NS; ++s) {
+      __syncthreads();
+      if (s + AH < NS) {
+        gload(s + AH, (s + AH) % RW);
+        uload(s + AH, (s + AH) % RU);
+      }
+      const bf16x8* ws = Ws[s % 3] + lane;
+#pragma unroll
+      for (int c = 0; c < SC2_KS; ++c) {
+        if (c == SC2_KS / 2 && s + 1 < NS) lstore((s + 1) % 3, (s + 1) % RW);
+#pragma unroll
+        for (int b = 0; b < NBW; ++b) {
+          const bf16x8 w = ws[((b0 + b) * SC2_KS + c) * 64];
+          acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % RU][c], w, acc[b], 0, 0, 0);
+        }
+      }
     }
-    __syncthreads();
-    const bf16x8* ws = Ws[s & 1] + lane;
+  } else {
+    // two LDS buffers: stage s's W is stored, then one barrier, then its MFMAs
 #pragma unroll
-    for (int c = 0; c < SC2_KS; ++c) {
+    for (int s = 0; s < NS; ++s) {
+      lstore(s & 1, s % RW);
+      if (s + AH < NS) {
+        gload(s + AH, s % RW);
+        uload(s + AH, (s + AH) % RU);
+      }
+      __syncthreads();
+      const bf16x8* ws = Ws[s & 1] + lane;
 #pragma unroll
-      for (int b = 0; b < SC2_NB; ++b) {
-        const bf16x8 w = ws[(b * SC2_KS + c) * 64];
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % RU][c], w, acc[b], 0, 0, 0);
+      for (int c = 0; c < SC2_KS; ++c) {
+#pragma unroll
+        for (int b = 0; b < NBW; ++b) {
+          const bf16x8 w = ws[((b0 + b) * SC2_KS + c) * 64];
+          acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % RU][c], w, acc[b], 0, 0, 0);
+        }
       }
     }
   }
 }
 
-#ifndef AA_SCREEN_OCC
-#define AA_SCREEN_OCC 2
-#endif
 template <int H>
-__global__ __launch_bounds__(256, AA_SCREEN_OCC) void k_vscreen2(int B, int V, int Vp, const bf16x8* __restrict__ ua,
+__global__ __launch_bounds__(256, 2) void k_vscreen2(int B, int V, int Vp, const bf16x8* __restrict__ ua,
                                                   const float* __restrict__ unorm, const bf16x8* __restrict__ wf,
                                                   const float4* __restrict__ gs, const float* __restrict__ bias,
                                                   float4* __restrict__ summ) {
@@ -2328,27 +2263,10 @@ __global__ __launch_bounds__(256, AA_SCREEN_OCC) void k_vscreen2(int B, int V, i
 #pragma unroll
   for (int b = 0; b < SC2_NB; ++b) bvs[b] = bias[n0 + 32 * b + li];
   floatx16 acc[SC2_NB];
-#ifndef AA_SCREEN_GS_LDS
-#define AA_SCREEN_GS_LDS 1
-#endif
-  // the granule bounds reach the epilogue through LDS (loaded before the main loop, no registers held
-  // across it) instead of by global loads inside the epilogue
-  screen2_main<H>(B, m0, n0, ua, unorm, wf, Ws, un_s, acc, AA_SCREEN_GS_LDS ? gs : nullptr, gs_s);
+  screen_main<H, 256, SC2_NB, false>(B, m0, n0, 0, ua, unorm, wf, Ws, un_s, acc, gs, gs_s);
   AA_TS(2, 1);
   const int row0 = m0 + 32 * wave;
-#ifndef AA_SCREEN_EPI
-#define AA_SCREEN_EPI 1
-#endif
-#if AA_SCREEN_EPI
-  screen_blocks_summ<H, SC2_NB>(acc, row0, n0 / VS_TILE, bvs, AA_SCREEN_GS_LDS ? gs_s : gs + n0 / VS_TILE,
-                             un_s + 32 * wave, n0, V, B, NTn, summ);
-#else
-#pragma unroll
-  for (int b = 0; b < SC2_NB; ++b) {
-    const int G = n0 / VS_TILE + b;
-    screen_block_summ<H>(acc[b], row0, G, bvs[b], gs[G], un_s + 32 * wave, n0 + 32 * b + li < V, B, NTn, summ);
-  }
-#endif
+  screen_blocks_summ<H, SC2_NB>(acc, row0, n0 / VS_TILE, bvs, gs_s, un_s + 32 * wave, n0, V, B, NTn, summ);
   AA_TS(2, 2);
 }
 
@@ -2359,104 +2277,6 @@ __global__ __launch_bounds__(256, AA_SCREEN_OCC) void k_vscreen2(int B, int V, i
 // LDS read (41 % of wave cycles waiting).  Every block accumulates its chunks in the
 // same order, so the summaries are k_vscreen2's bit for bit.
 constexpr int SC8_NT = 512, SC8_NA = 3, SC8_NBB = SC2_NB - SC8_NA;  // threads; blocks of group 0 / 1
-#ifndef AA_SCREEN8_RING3
-#define AA_SCREEN8_RING3 1
-#endif
-template <int H, int NBW>
-__device__ __forceinline__ void screen8_main(int B, int m0, int n0, int b0, const bf16x8* __restrict__ ua,
-                                             const float* __restrict__ unorm, const bf16x8* __restrict__ wf,
-                                             bf16x8 (*Ws)[SC2_STAGE], float2* un_s, floatx16 (&acc)[NBW],
-                                             const float4* __restrict__ gs, float4* gs_s) {
-  constexpr int KC = H / 16, NS = KC / SC2_KS, PER = (SC2_STAGE + SC8_NT - 1) / SC8_NT;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const bf16x8* a0 = ua + (size_t)((m0 >> 5) + (wave & 3)) * KC * 64 + lane;
-#ifndef AA_SCREEN8_AHEAD
-#define AA_SCREEN8_AHEAD 2
-#endif
-  constexpr int AH = AA_SCREEN8_AHEAD < NS ? AA_SCREEN8_AHEAD : NS, RW = AH, RU = AH + 1;
-  bf16x8 fa[RU][SC2_KS];
-  auto uload = [&](int s, int slot) {
-#pragma unroll
-    for (int c = 0; c < SC2_KS; ++c) fa[slot][c] = a0[(size_t)(s * SC2_KS + c) * 64];
-  };
-  const bf16x8* wbase = wf + (size_t)(n0 >> 5) * KC * 64;
-  bf16x8 wr[RW][PER];
-  auto gload = [&](int s, int slot) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int j = t + SC8_NT * i;
-      if (PER * SC8_NT == SC2_STAGE || j < SC2_STAGE) {  // (wave-uniform)
-        const int b = j / (SC2_KS * 64), r = j - b * (SC2_KS * 64);
-        wr[slot][i] = wbase[((size_t)b * KC + s * SC2_KS) * 64 + r];
-      }
-    }
-  };
-  auto lstore = [&](int buf, int slot) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int j = t + SC8_NT * i;
-      if (PER * SC8_NT == SC2_STAGE || j < SC2_STAGE) Ws[buf][j] = wr[slot][i];
-    }
-  };
-#pragma unroll
-  for (int s = 0; s < AH; ++s) uload(s, s);
-#pragma unroll
-  for (int b = 0; b < NBW; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-#pragma unroll
-  for (int s = 0; s < AH; ++s) gload(s, s);
-  if (t < SC2_BM) {
-    const int r = m0 + t;
-    un_s[t] = make_float2(unorm[r < B ? r : B - 1], unorm[B + (r < B ? r : B - 1)]);
-  } else if (t < SC2_BM + SC2_NB) {
-    gs_s[t - SC2_BM] = gs[n0 / VS_TILE + t - SC2_BM];
-  }
-#if AA_SCREEN8_RING3
-  // three LDS buffers (the default): stage s + 1's W is stored in the middle of stage s's MFMAs (its
-  // buffer was last read in stage s - 2, before this stage's barrier), so the store's latency is off
-  // the barrier -> read -> MFMA path; one barrier per stage.  10.1 -> 9.7 us, sequential decode
-  // +0.7 % (A/B, profiles/r06i_screen_ring3_ab.txt); four stages ahead of the W / u loads: no gain
-  lstore(0, 0);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    __syncthreads();
-    if (s + AH < NS) {
-      gload(s + AH, (s + AH) % RW);
-      uload(s + AH, (s + AH) % RU);
-    }
-    const bf16x8* ws = Ws[s % 3] + lane;
-#pragma unroll
-    for (int c = 0; c < SC2_KS; ++c) {
-      if (c == SC2_KS / 2 && s + 1 < NS) lstore((s + 1) % 3, (s + 1) % RW);
-#pragma unroll
-      for (int b = 0; b < NBW; ++b) {
-        const bf16x8 w = ws[((b0 + b) * SC2_KS + c) * 64];
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % RU][c], w, acc[b], 0, 0, 0);
-      }
-    }
-  }
-#else
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    lstore(s & 1, s % RW);
-    if (s + AH < NS) {
-      gload(s + AH, s % RW);
-      uload(s + AH, (s + AH) % RU);
-    }
-    __syncthreads();
-    const bf16x8* ws = Ws[s & 1] + lane;
-#pragma unroll
-    for (int c = 0; c < SC2_KS; ++c) {
-#pragma unroll
-      for (int b = 0; b < NBW; ++b) {
-        const bf16x8 w = ws[((b0 + b) * SC2_KS + c) * 64];
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % RU][c], w, acc[b], 0, 0, 0);
-      }
-    }
-  }
-#endif
-}
 template <int H, int NBW>
 __device__ __forceinline__ void screen8_group(int B, int V, int m0, int n0, int b0, int NTn,
                                               const bf16x8* __restrict__ ua, const float* __restrict__ unorm,
@@ -2468,7 +2288,7 @@ __device__ __forceinline__ void screen8_group(int B, int V, int m0, int n0, int 
 #pragma unroll
   for (int b = 0; b < NBW; ++b) bvs[b] = bias[n0 + 32 * (b0 + b) + li];
   floatx16 acc[NBW];
-  screen8_main<H, NBW>(B, m0, n0, b0, ua, unorm, wf, Ws, un_s, acc, gs, gs_s);
+  screen_main<H, SC8_NT, NBW, true>(B, m0, n0, b0, ua, unorm, wf, Ws, un_s, acc, gs, gs_s);
   AA_TS(2, 1);
   const int row0 = m0 + 32 * (wave & 3);
   screen_blocks_summ<H, NBW>(acc, row0, n0 / VS_TILE + b0, bvs, gs_s + b0, un_s + 32 * (wave & 3), n0 + 32 * b0, V, B,
@@ -2479,7 +2299,7 @@ __global__ __launch_bounds__(SC8_NT) void k_vscreen8(int B, int V, int Vp, const
                                                      const float* __restrict__ unorm, const bf16x8* __restrict__ wf,
                                                      const float4* __restrict__ gs, const float* __restrict__ bias,
                                                      float4* __restrict__ summ) {
-  __shared__ __attribute__((aligned(16))) bf16x8 Ws[AA_SCREEN8_RING3 ? 3 : 2][SC2_STAGE];
+  __shared__ __attribute__((aligned(16))) bf16x8 Ws[3][SC2_STAGE];
   __shared__ float2 un_s[SC2_BM];
   __shared__ float4 gs_s[SC2_NB];
   AA_TS(2, 0);
@@ -2487,6 +2307,10 @@ __global__ __launch_bounds__(SC8_NT) void k_vscreen8(int B, int V, int Vp, const
   const int L = xcd_remap(blockIdx.x, MT * NT);
   const int nt = L / MT, mt = L % MT;  // m fastest: a W tile is shared inside an XCD
   const int m0 = mt * SC2_BM, n0 = nt * SC2_BN;
+  // The two groups run different instantiations of the main loop and the epilogue, each with its own
+  // __syncthreads() calls (the same number on both sides).  This relies on the hardware barrier
+  // counting the workgroup's waves whichever code path each arrives from; AA_DECODE_SCREEN4's bitwise
+  // test against k_vscreen2 is the guard.
   if (threadIdx.x < 256)  // (wave-uniform) column blocks 0..2
     screen8_group<H, SC8_NA>(B, V, m0, n0, 0, NTn, ua, unorm, wf, gs, bias, summ, Ws, un_s, gs_s);
   else                    // column blocks 3..4
@@ -2536,10 +2360,7 @@ __device__ __forceinline__ float exact_logit8(const float* __restrict__ urow, co
 // tried: each wave reading the W row of its best granule's arg-max column before the barriers, as a
 // cache warm-up for the likely winner: k_vrescore 9.95 -> 10.4 us by events in A/B.)
 // ---------------------------------------------------------------------------------------------
-#ifndef AA_RS_THREADS
-#define AA_RS_THREADS 256
-#endif
-constexpr int RS_NT = AA_RS_THREADS, RS_NW = RS_NT / 64;
+constexpr int RS_NT = 256, RS_NW = RS_NT / 64;
 // LDS scratch of one rescored row (floats): u row, candidate list, count, wave maxima, wave keys
 template <int H>
 struct RsScratch {
@@ -3057,7 +2878,7 @@ static int encoder_launch(const Layout& L, const MP& p, const float* feats, int 
     // then runs on aux beside the VWv GEMM.  (Trace: the fused avg-pool is a zero-length pair.)
     const int nwg = (B * P + E4_ROWS - 1) / E4_ROWS;
     if (H == 512)
-      AA_TLAUNCH(ev, 2, (k_enc_v4<32 / AA_ENC4_NW, AA_ENC4_NW>), dim3(nwg), dim3(64 * AA_ENC4_NW), 0, s, feats, B, C,
+      AA_TLAUNCH(ev, 2, (k_enc_v4<32 / ENC4_NW, ENC4_NW>), dim3(nwg), dim3(64 * ENC4_NW), 0, s, feats, B, C,
                  (const bf16x8*)p.enc_w4, (const float*)p.enc_a_b, V, a_g);
     else
       AA_TLAUNCH(ev, 2, k_enc_v4<2>, dim3(nwg), dim3(512), 0, s, feats, B, C, (const bf16x8*)p.enc_w4,
@@ -3215,32 +3036,22 @@ static void lstm_launch(const Layout& L, const MP& p, int B, const int64_t* tok,
   const int H = L.H, MT = (B + 63) / 64;
   const RsArgs none{};
   const int64_t* tnull = nullptr;
-#define AA_LSTM(H_)                                                                                          \
-  do {                                                                                                       \
-    if (par)                                                                                                 \
-      AA_TLAUNCH(ev, ei, (k_lstm<H_, true>), dim3(MT * (H_ / 16)), dim3(512), 0, s, B, L.V, tok, tok_ld,     \
-                 p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);    \
-    else if (ra)                                                                                             \
-      AA_TLAUNCH(ev, ei, (k_lstm<H_, false, true>), dim3(ra->NR + MT * (H_ / 16)), dim3(512), 0, s, B, L.V,   \
-                 tnull, 0, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part,  \
-                 *ra);                                                                                       \
-    else                                                                                                     \
-      AA_TLAUNCH(ev, ei, (k_lstm<H_, false>), dim3(MT * (H_ / 16)), dim3(512), 0, s, B, L.V, tok, tok_ld,    \
-                 p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);    \
-  } while (0)
-  switch (H) {
-    case 256: AA_LSTM(256); break;
-    case 512: AA_LSTM(512); break;
-    case 768: AA_LSTM(768); break;
-    default: AA_LSTM(1024); break;
-  }
-#undef AA_LSTM
+  aa_for_hidden(H, [&](auto h) {
+    constexpr int H_ = h.value;
+    if (par)
+      AA_TLAUNCH(ev, ei, (k_lstm<H_, true>), dim3(MT * (H_ / 16)), dim3(512), 0, s, B, L.V, tok, tok_ld,
+                 p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);
+    else if (ra)
+      AA_TLAUNCH(ev, ei, (k_lstm<H_, false, true>), dim3(ra->NR + MT * (H_ / 16)), dim3(512), 0, s, B, L.V,
+                 tnull, 0, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part,
+                 *ra);
+    else
+      AA_TLAUNCH(ev, ei, (k_lstm<H_, false>), dim3(MT * (H_ / 16)), dim3(512), 0, s, B, L.V, tok, tok_ld,
+                 p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);
+  });
 }
 
 // Attention for one step (kdiv rows per image: beam search; k_atten5b runs an image's rows together)
-#ifndef AA_ATTEN_BEAM
-#define AA_ATTEN_BEAM 1
-#endif
 static void atten_launch(const Layout& L, const MP& p, int B, const float* V, const float* vwv, const float* h_out,
                          float* s_buf, float* part, float* u, uint16_t* ub, float* unorm, float* alpha,
                          int64_t alpha_ld, float* beta, int64_t beta_ld, hipStream_t s, int kdiv = 1,
@@ -3257,7 +3068,7 @@ static void atten_launch(const Layout& L, const MP& p, int B, const float* V, co
 #define AA_ATTEN5B(KB_)                                                                                    \
   AA_TLAUNCH(ev, ei, (k_atten5b<512, KB_>), dim3(B / KB_), dim3(512), 0, s, h_out, sb, pt, V, vwv, p.wh, alpha, \
              alpha_ld, beta, beta_ld, u, ub, unorm, ub3)
-  if (H == 512 && kdiv >= 2 && kdiv <= 5 && B % kdiv == 0 && AA_ATTEN_BEAM) {  // beam: one workgroup per image
+  if (H == 512 && kdiv >= 2 && kdiv <= 5 && B % kdiv == 0) {  // beam: one workgroup per image
     switch (kdiv) {
       case 2: AA_ATTEN5B(2); break;
       case 3: AA_ATTEN5B(3); break;
@@ -3366,43 +3177,31 @@ static int decode_rows(const Layout& L, const MP& p, const DecodeWS& w, int B, i
       hipLaunchKernelGGL(k_key_ids, dim3((B + 255) / 256), dim3(256), 0, s, kt, B, ids + t, T);
       continue;
     }
-#define AA_SCREEN(H_)                                                                                          \
-  AA_TLAUNCH(sev, 2 * t, k_vscreen<H_>, dim3(((B + SC_BM - 1) / SC_BM) * (L.Vp / SC_BN)), dim3(256), 0, s, B, L.V, \
-             L.Vp, reinterpret_cast<const bf16x8*>(w.ub), (const float*)w.unorm,                                  \
-             reinterpret_cast<const bf16x8*>(p.mlp_wb), p.mlp_gs, p.mlp_b, w.summ)
-#ifndef AA_SCREEN8
-#define AA_SCREEN8 1
-#endif
-#define AA_SCREEN2(H_)                                                                                          \
-  do {                                                                                                         \
-    if (AA_SCREEN8 && !(flags & AA_DECODE_SCREEN4))                                                            \
-      AA_TLAUNCH(sev, 2 * t, k_vscreen8<H_>, dim3(((B + SC2_BM - 1) / SC2_BM) * (L.Vp / SC2_BN)), dim3(SC8_NT), 0, \
-                 s, B, L.V, L.Vp, reinterpret_cast<const bf16x8*>(w.ub), (const float*)w.unorm,                \
-                 reinterpret_cast<const bf16x8*>(p.mlp_wb), p.mlp_gs, p.mlp_b, w.summ);                        \
-    else                                                                                                       \
-      AA_TLAUNCH(sev, 2 * t, k_vscreen2<H_>, dim3(((B + SC2_BM - 1) / SC2_BM) * (L.Vp / SC2_BN)), dim3(256), 0, s, \
-                 B, L.V, L.Vp, reinterpret_cast<const bf16x8*>(w.ub), (const float*)w.unorm,                   \
-                 reinterpret_cast<const bf16x8*>(p.mlp_wb), p.mlp_gs, p.mlp_b, w.summ);                        \
-  } while (0)
-#define AA_RESCORE(H_)                                                                                          \
-  AA_TLAUNCH(rev, 2 * t, k_vrescore<H_>, dim3(B), dim3(RS_NT), 0, s, B, L.V, L.Vp, (const float*)w.u,           \
-             (const float4*)w.summ, p.mlp_w, p.mlp_b, kt, ids, T, t)
-    switch (H) {
-      case 256: if (wide) AA_SCREEN2(256); else AA_SCREEN(256); break;
-      case 512: if (wide) AA_SCREEN2(512); else AA_SCREEN(512); break;
-      case 768: AA_SCREEN(768); break;
-      default: AA_SCREEN(1024); break;
-    }
+    const bf16x8* ubf = reinterpret_cast<const bf16x8*>(w.ub);
+    const bf16x8* wbf = reinterpret_cast<const bf16x8*>(p.mlp_wb);
+    const float* unorm = w.unorm;
+    aa_for_hidden(H, [&](auto h) {
+      constexpr int H_ = h.value;
+      const dim3 g2(((B + SC2_BM - 1) / SC2_BM) * (L.Vp / SC2_BN));
+      if constexpr (H_ <= 512) {  // screen_wide() admits no larger H: no k_vscreen8 / k_vscreen2 beyond it
+        if (wide) {
+          if (!(flags & AA_DECODE_SCREEN4))
+            AA_TLAUNCH(sev, 2 * t, k_vscreen8<H_>, g2, dim3(SC8_NT), 0, s, B, L.V, L.Vp, ubf, unorm, wbf, p.mlp_gs,
+                       p.mlp_b, w.summ);
+          else
+            AA_TLAUNCH(sev, 2 * t, k_vscreen2<H_>, g2, dim3(256), 0, s, B, L.V, L.Vp, ubf, unorm, wbf, p.mlp_gs,
+                       p.mlp_b, w.summ);
+          return;
+        }
+      }
+      AA_TLAUNCH(sev, 2 * t, k_vscreen<H_>, dim3(((B + SC_BM - 1) / SC_BM) * (L.Vp / SC_BN)), dim3(256), 0, s, B, L.V,
+                 L.Vp, ubf, unorm, wbf, p.mlp_gs, p.mlp_b, w.summ);
+    });
     if (fused && t + 1 < T) continue;  // rescored by step t+1's k_lstm
-    switch (H) {
-      case 256: AA_RESCORE(256); break;
-      case 512: AA_RESCORE(512); break;
-      case 768: AA_RESCORE(768); break;
-      default: AA_RESCORE(1024); break;
-    }
-#undef AA_SCREEN
-#undef AA_SCREEN2
-#undef AA_RESCORE
+    aa_for_hidden(H, [&](auto h) {
+      AA_TLAUNCH(rev, 2 * t, k_vrescore<h.value>, dim3(B), dim3(RS_NT), 0, s, B, L.V, L.Vp, (const float*)w.u,
+                 (const float4*)w.summ, p.mlp_w, p.mlp_b, kt, ids, T, t);
+    });
   }
   return launch_status();
 }

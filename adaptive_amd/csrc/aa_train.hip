@@ -342,155 +342,6 @@ static void reduce_launch(const TG& g, hipStream_t s) {
     hipLaunchKernelGGL(k_tgemm_reduce, dim3((unsigned)(((int64_t)g.M * g.N + 255) / 256)), dim3(256), 0, s, g);
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_tgemm on 128 x 128 tiles for a bf16 step (AA_TRAIN_BF16): the same operand layouts (A
-// row-major or transposed, W in layouts 0 / 1), RNE rounding while staging, bias / act / row maps /
-// accumulate and split-K partials as k_tgemm; a workgroup computes a 128 x 128 tile (four waves of
-// 64 x 64 = 2 x 2 v_mfma_f32_32x32x16_bf16 blocks, k_bgemm's MFMA arrangement), 64-deep K steps
-// double-buffered in LDS.  Twice k_tgemm's FLOP per staged byte and four MFMAs per fragment pair read.
-// LDS rows of 72 bf16 (144 B) with the 16-B chunk index XOR-swizzled by (row / 8) % 8: the
-// transposed operands are staged as 2-byte stores down a column of rows 8 apart, which without the
-// swizzle fall into two banks (8-way conflicts); with it into 16.  The 16-B fragment reads stay
-// conflict-free (8 consecutive rows share the swizzle).
-// ---------------------------------------------------------------------------------------------
-constexpr int T8_T = 128, T8_KS = 64, T8_LD = T8_KS + 8;
-__device__ __forceinline__ int t8_off(int r, int k) {  // bf16 index of (row r, k) in a swizzled tile
-  return r * T8_LD + ((((k >> 3) ^ (r >> 3)) & 7) << 3) + (k & 7);
-}
-__global__ __launch_bounds__(256, 2) void k_tgemm128(TG g) {
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2][2][T8_T * T8_LD];
-  const int tilesN = (g.N + T8_T - 1) / T8_T;
-  const int split = blockIdx.x % g.splits, tile = blockIdx.x / g.splits;
-  const int mt = tile / tilesN, nt = tile % tilesN;
-  const int kbeg = split * g.kper, kend = g.splits > 1 ? (kbeg + g.kper < g.K ? kbeg + g.kper : g.K) : g.K;
-  const int m0 = mt * T8_T, n0 = nt * T8_T;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  const bool a4 = ((g.lda & 3) == 0) && ((((uintptr_t)g.A) & 15) == 0);
-  const bool w4 = ((g.ldw & 3) == 0) && ((((uintptr_t)g.W) & 15) == 0);
-  float ra[4][8], rw[4][8];
-  auto load8 = [&](float (&r)[8], const float* base) {
-    const float4 x = *reinterpret_cast<const float4*>(base), y = *reinterpret_cast<const float4*>(base + 4);
-    r[0] = x.x; r[1] = x.y; r[2] = x.z; r[3] = x.w; r[4] = y.x; r[5] = y.y; r[6] = y.z; r[7] = y.w;
-  };
-  // piece i of this thread: K-contiguous operands (A with at = 0, W with wm = 0) -> row q >> 3,
-  // k 8 (q & 7) (8 lanes per 256-B row segment); transposed ones -> k q >> 4, rows 8 (q & 15) .. + 7
-  // (16 lanes per 512-B segment of a k row); q = t + 256 i
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = t + 256 * i;
-      if (!g.at) {
-        const int r = q >> 3, kq = (q & 7) * 8, m = m0 + r, k = k0 + kq;
-        const int64_t base = (int64_t)(m < g.M ? (g.arow ? g.arow[m] : m) : 0) * g.lda;
-        if (a4 && m < g.M && k + 8 <= kend) load8(ra[i], g.A + base + k);
-        else
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ra[i][e] = (m < g.M && k + e < kend) ? g.A[base + k + e] : 0.f;
-      } else {
-        const int k = k0 + (q >> 4), mq = m0 + (q & 15) * 8;
-        if (a4 && k < kend && mq + 8 <= g.M) load8(ra[i], g.A + (int64_t)k * g.lda + mq);
-        else
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ra[i][e] = (k < kend && mq + e < g.M) ? g.A[(int64_t)k * g.lda + mq + e] : 0.f;
-      }
-      if (g.wm == 0) {
-        const int r = q >> 3, kq = (q & 7) * 8, n = n0 + r, k = k0 + kq;
-        const int64_t base = (int64_t)(n < g.N ? n : 0) * g.ldw;
-        if (w4 && n < g.N && k + 8 <= kend) load8(rw[i], g.W + base + k);
-        else
-#pragma unroll
-          for (int e = 0; e < 8; ++e) rw[i][e] = (n < g.N && k + e < kend) ? g.W[base + k + e] : 0.f;
-      } else {
-        const int k = k0 + (q >> 4), nq = n0 + (q & 15) * 8;
-        if (w4 && k < kend && nq + 8 <= g.N) load8(rw[i], g.W + (int64_t)k * g.ldw + nq);
-        else
-#pragma unroll
-          for (int e = 0; e < 8; ++e) rw[i][e] = (k < kend && nq + e < g.N) ? g.W[(int64_t)k * g.ldw + nq + e] : 0.f;
-      }
-    }
-  };
-  auto lstore = [&](int buf) {
-    __bf16* As = lds[buf][0];
-    __bf16* Ws = lds[buf][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = t + 256 * i;
-      if (!g.at) {
-        bf16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (__bf16)ra[i][e];
-        *reinterpret_cast<bf16x8*>(As + t8_off(q >> 3, (q & 7) * 8)) = v;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) As[t8_off((q & 15) * 8 + e, q >> 4)] = (__bf16)ra[i][e];
-      }
-      if (g.wm == 0) {
-        bf16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (__bf16)rw[i][e];
-        *reinterpret_cast<bf16x8*>(Ws + t8_off(q >> 3, (q & 7) * 8)) = v;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) Ws[t8_off((q & 15) * 8 + e, q >> 4)] = (__bf16)rw[i][e];
-      }
-    }
-  };
-  floatx16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
-  const int nk = (kend - kbeg + T8_KS - 1) / T8_KS;
-  gload(kbeg);
-  lstore(0);
-  __syncthreads();
-  for (int ks = 0; ks < nk; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nk) gload(kbeg + (ks + 1) * T8_KS);
-    const __bf16* As = lds[buf][0];
-    const __bf16* Ws = lds[buf][1];
-#pragma unroll
-    for (int kb = 0; kb < T8_KS / 16; ++kb) {
-      bf16x8 a[2], b[2];
-#pragma unroll
-      for (int x = 0; x < 2; ++x) a[x] = *reinterpret_cast<const bf16x8*>(As + t8_off(wm * 64 + x * 32 + li, 16 * kb + 8 * lh));
-#pragma unroll
-      for (int y = 0; y < 2; ++y) b[y] = *reinterpret_cast<const bf16x8*>(Ws + t8_off(wn * 64 + y * 32 + li, 16 * kb + 8 * lh));
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x], b[y], acc[x][y], 0, 0, 0);
-    }
-    if (ks + 1 < nk) lstore(buf ^ 1);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int y = 0; y < 2; ++y) {
-    const int col = n0 + wn * 64 + y * 32 + li;
-    if (col >= g.N) continue;
-    const float bv = (g.bias ? g.bias[col] : 0.f) + (g.bias2 ? g.bias2[col] : 0.f);
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + x * 32 + acc_row(r, lane);
-        if (m >= g.M) continue;
-        if (g.splits > 1) {
-          g.part[(int64_t)split * g.M * g.N + (int64_t)m * g.N + col] = acc[x][y][r];
-        } else {
-          float v = acc[x][y][r] + bv;
-          if (g.act == 1) v = reluf_(v);
-          else if (g.act == 2) v = tanhf(v);
-          float* dst = g.C + (int64_t)(g.crow ? g.crow[m] : m) * g.ldc + col;
-          *dst = g.accumulate ? *dst + v : v;
-        }
-      }
-  }
-}
-
 // k_tgemm's split-K bound (floats of partials): its split counts, and so its fp32 sums, as before
 // the scratch grew for k_bgemm
 constexpr size_t TG_SPLIT_CAP = (size_t)4 << 20;
@@ -520,46 +371,14 @@ static int tgemm(const GemmCtx& gc, int M, int N, int K, const float* A, int64_t
     return e && atoi(e) == 1;
   }();
   if (tlog) fprintf(stderr, "tgemm M %d N %d K %d at %d wm %d acc %d stream %p\n", M, N, K, at, wm, accumulate, (void*)s);
-  // AA_TG128=1, bf16 weight gradients (both operands transposed, K >= 1024: dW_hh, dW_ih, dW_x, dW_h
-  // over all T B rows): 128 x 128 tiles (k_tgemm128), split along K to ~512 workgroups (>= 256 deep
-  // each) -- 30.7 / 31.0 us against 41.7 / 76.1 us for dW_hh / dW_ih on the 64 x 64 engine (split to
-  // 1024 workgroups, four times the partials), but they run on the aux stream beside the LSTM
-  // backward and the whole step did not gain (750 vs 752 steps/s); for the GEMMs reading one operand
-  // along K the 64 x 64 engine measured faster (profiles/r06v_train_gemm_engines.txt)
-  static const bool t128 = [] {  // AA_TG128=1: the deep weight gradients on k_tgemm128 (off: no gain in the step)
-    const char* e = getenv("AA_TG128");
-    return e && atoi(e) == 1;
-  }();
-  if (t128 && gc.bf16 && at == 1 && wm == 1 && M >= 128 && N >= 128 && (int64_t)M * N >= 128 * 256 && K >= 1024) {
-    const int tiles8 = ((M + T8_T - 1) / T8_T) * ((N + T8_T - 1) / T8_T);
-    int sp = 1;
-    if (tiles8 < 256 && K >= 512 && gc.split) {
-      sp = (512 + tiles8 - 1) / tiles8;
-      if (sp > K / 256) sp = K / 256;
-      const size_t capsp = gc.cap / ((size_t)M * N);
-      if ((size_t)sp > capsp) sp = (int)capsp;
-      if (sp < 2) sp = 1;
-    }
-    int kp = K;
-    if (sp > 1) {
-      kp = ((K + sp - 1) / sp + T8_KS - 1) / T8_KS * T8_KS;
-      sp = (K + kp - 1) / kp;
-    }
-    TG g{M, N, K, A, lda, arow, at, W, ldw, wm, C, ldc, crow, bias, bias2, accumulate, act, sp, kp,
-         sp > 1 ? gc.split : nullptr};
-    hipLaunchKernelGGL(k_tgemm128, dim3(tiles8 * sp), dim3(256), 0, s, g);
-    if (sp > 1 && !defer) reduce_launch(g, s);
-    return sp;
-  }
   const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
   int splits = 1;
   // few tiles: split to ~256 workgroups (>= 128 deep each); long K over < 512 tiles (the vocab-sized
   // backward GEMMs, the weight gradients over all T*B rows): split to ~1024 (>= 512 deep each)
   const bool small = tiles < 128 && K >= 256, deep = tiles < 512 && K >= 1024;
-  static const int deep_wg = [] {  // AA_TG_DEEP_WG: workgroups a deep split aims at (A/B probe)
-    const char* e = getenv("AA_TG_DEEP_WG");
-    return e ? atoi(e) : 1024;
-  }();
+  // workgroups a deep split aims at (512 / 256 measured within one box's noise of 1024:
+  // profiles/r06z3_train_bgemm_split_ab.txt)
+  constexpr int deep_wg = 1024;
   if ((small || deep) && gc.split) {
     splits = small ? (256 + tiles - 1) / tiles : (deep_wg + tiles - 1) / tiles;
     const int kmax = K / (small ? 128 : 512);
@@ -824,16 +643,15 @@ __global__ void k_pk_feats(const float* __restrict__ feats, int B, int C, __bf16
 }
 
 // C[M,N] (+)= A B^T (+ bias) on k_bgemm; K a multiple of 64.  Fewer than 512 tiles: split K to
-// ~1024 workgroups (bounded by the split scratch), partials reduced by k_tgemm_reduce in split order.
+// ~256 workgroups (bounded by the split scratch), partials reduced by k_tgemm_reduce in split order.
 static void bgemm(const GemmCtx& gc, int M, int N, int K, const __bf16* A, int64_t lda, const __bf16* B, int64_t ldb,
                   float* C, int64_t ldc, const float* bias = nullptr, const int* crow = nullptr, int accumulate = 0,
                   int act = 0) {
   if (M <= 0 || N <= 0 || K <= 0) return;
   const int tiles = ((M + BG_T - 1) / BG_T) * ((N + BG_T - 1) / BG_T), ksteps = K / BG_KS;
-  static const int wg_target = [] {  // AA_BG_WG: workgroups a split k_bgemm aims at (A/B probe)
-    const char* e = getenv("AA_BG_WG");
-    return e ? atoi(e) : 256;
-  }();
+  // workgroups a split launch aims at: 64 / 128 / 192 / 512 / 1024 / 2048 measured no better (at 1024
+  // dU's split writes 18 partial sets where 256 writes 5: profiles/r06z3_train_bgemm_split_ab.txt)
+  constexpr int wg_target = 256;
   int splits = tiles >= 512 ? 1 : (wg_target + tiles - 1) / tiles;
   if (splits > ksteps) splits = ksteps;
   const size_t capsp = gc.split ? gc.cap / ((size_t)M * N) : 1;
@@ -1038,71 +856,22 @@ __global__ void k_copy_cols(const float* __restrict__ src, int64_t lds, int c0, 
   dst[(int64_t)r * ldd + c] = src[(int64_t)r * lds + c0 + c];
 }
 
-// Atten.forward for one (t, b) row (adaptive_attention.py:34-56), projections precomputed:
-// PG = W_g h_t, PS = W_s s_t (row pitch PP), VWv[b] = W_v V_b.  Writes alpha (pitch PP), beta,
-// the context c_t and u = c_hat + h_t (the mlp input, :132).  256 threads.
-__global__ __launch_bounds__(256) void k_tr_atten(int B, int H, const float* __restrict__ PG, const float* __restrict__ PS,
-                                                  const float* __restrict__ VWv, const float* __restrict__ Vf,
-                                                  const float* __restrict__ wh, const float* __restrict__ Hs,
-                                                  const float* __restrict__ S, float* __restrict__ alpha,
-                                                  float* __restrict__ beta, float* __restrict__ ctx,
-                                                  float* __restrict__ U) {
-  __shared__ float zs[PP], al[PP], sh_b;
-  const int r = blockIdx.x, b = r % B, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const float* pg = PG + (int64_t)r * PP;
-  // scores z_k = w_h . tanh(VWv[b][k] + PG), k < 49; z_s = w_h . tanh(PS + PG): one wave per item
-  for (int k = w; k <= P; k += 4) {
-    float z = 0.f;
-    if (lane < P) {
-      const float x = (k < P ? VWv[((int64_t)b * P + k) * PP + lane] : PS[(int64_t)r * PP + lane]) + pg[lane];
-      z = wh[lane] * tanhf(x);
-    }
-    z = wave_sum(z);
-    if (lane == 0) zs[k] = z;
-  }
-  __syncthreads();
-  if (w == 0) {  // softmax_49 (alpha), softmax_50 (beta = its last entry)
-    const float z = lane < P ? zs[lane] : -INFINITY;
-    const float m = wave_max(z);
-    const float e = lane < P ? expf(z - m) : 0.f;
-    const float a = e / wave_sum(e);
-    if (lane < P) {
-      al[lane] = a;
-      alpha[(int64_t)r * PP + lane] = a;
-    }
-    const float zsn = zs[P];
-    const float m2 = fmaxf(m, zsn);
-    const float e2 = lane < P ? expf(z - m2) : 0.f;
-    const float es = expf(zsn - m2);
-    const float S2 = wave_sum(e2) + es;
-    if (lane == 0) {
-      sh_b = es / S2;
-      beta[r] = es / S2;
-    }
-  }
-  __syncthreads();
-  const float be = sh_b;
-  const float* vb = Vf + (int64_t)b * P * H;
-  for (int d = t; d < H; d += 256) {
-    float c = 0.f;
-    for (int k = 0; k < P; ++k) c = __builtin_fmaf(al[k], vb[(int64_t)k * H + d], c);
-    ctx[(int64_t)r * H + d] = c;
-    const float chat = be * S[(int64_t)r * H + d] + (1.f - be) * c;
-    U[(int64_t)r * H + d] = chat + Hs[(int64_t)r * H + d];
-  }
-}
-
-// k_tr_atten's rows grouped by image, in three phases instead of a per-row chain: one workgroup of H
-// threads per (image b, group of TS <= 32 consecutive steps).  V_b stays in registers (thread d holds
-// column d: 49 floats), VWv_b and the group's PG / PS rows in LDS.
-//   A: every (row, item) score of the group at once, one per thread: z = w_h . tanh(x) summed by the
-//      same pairing tree as wave_sum's xor butterfly (a[i] += a[i + o], o = 32 .. 1, entries >= 49 zero),
-//      so z is bit-identical to k_tr_atten's wave-cooperative sum, with no cross-lane dependence;
-//   B: the two softmaxes, one wave per row, exactly as k_tr_atten;
-//   C: the context of every row of the group, one fma chain over k per column, and u = c_hat + h.
-// V_b and VWv_b are read once per group instead of once per row (2304 x 100 KB per training step at
-// B = 128, T = 18), and the rows' scores run side by side rather than one wave-reduction at a time:
-// bit-identical outputs to k_tr_atten.
+// Atten.forward (adaptive_attention.py:34-56) for every (t, b) row r = t B + b, projections
+// precomputed: PG = W_g h_t, PS = W_s s_t (row pitch PP), VWv[b] = W_v V_b.  Writes alpha (pitch PP),
+// beta, the context c_t and u = c_hat + h_t (the mlp input, :132).  The rows are grouped by image:
+// one workgroup of H threads per (image b, group of TS <= 32 consecutive steps), so V_b and VWv_b are
+// read once per group instead of once per row (2304 x 100 KB per training step at B = 128, T = 18).
+// V_b stays in registers (thread d holds column d: 49 floats), VWv_b and the group's PG / PS rows in
+// LDS.  Three phases, each with a fixed summation order (a step's bits do not depend on TS or on the
+// grid):
+//   A: every (row, item) score of the group at once, one per thread: z_k = w_h . tanh(VWv[b][k] + PG),
+//      k < 49; z_s = w_h . tanh(PS + PG).  The 64 terms (entries >= 49 zero) are summed by the pairing
+//      tree of wave_sum's xor butterfly, a[i] += a[i + o] for o = 32 .. 1 -- the order a
+//      wave-cooperative sum over lanes gives -- with no cross-lane dependence;
+//   B: softmax_49 (alpha) and softmax_50 (beta = its last entry), one wave per row: wave_max,
+//      wave_sum of exp(z - m), and for beta exp against max(m, z_s) with z_s's term added last;
+//   C: the context of every row of the group, one fma chain over k = 0 .. 48 per column, then
+//      c_hat = beta s + (1 - beta) c and u = c_hat + h.
 constexpr int TRA_TS = 32;  // steps per group, at most
 template <int H>
 __global__ __launch_bounds__(H) void k_tr_atten_img(int B, int T, int TS, const float* __restrict__ PG,
@@ -1927,20 +1696,14 @@ static void decoder_core(const GemmCtx& gc, const aa_ref_weights* w, const Train
       const float* cp = t ? s.Cs + (size_t)(t - 1) * B * H : s.c0;
       const float* pre = s.PRE + (size_t)t * B * 5 * H;
       float *ho = s.Hs + (size_t)t * B * H, *co = s.Cs + (size_t)t * B * H, *ga = s.GA + (size_t)t * B * 4 * H;
-#define AA_LF(H_)                                                                                                  \
-  if (t == 0)                                                                                                      \
-    hipLaunchKernelGGL((k_tr_lstm_f<H_, true>), dim3(grid), dim3(256), 0, st, B, (const void*)s.h0, pre, 5 * H, cp, \
-                       s.whf, ho, co, ga, s.hb[0]);                                                              \
-  else                                                                                                             \
-    hipLaunchKernelGGL((k_tr_lstm_f<H_, false>), dim3(grid), dim3(256), 0, st, B, (const void*)s.hb[(t - 1) & 1],  \
-                       pre, 5 * H, cp, s.whf, ho, co, ga, s.hb[t & 1])
-      switch (H) {
-        case 256: AA_LF(256); break;
-        case 512: AA_LF(512); break;
-        case 768: AA_LF(768); break;
-        default: AA_LF(1024); break;
-      }
-#undef AA_LF
+      aa_for_hidden(H, [&](auto h) {
+        if (t == 0)
+          hipLaunchKernelGGL((k_tr_lstm_f<h.value, true>), dim3(grid), dim3(256), 0, st, B, (const void*)s.h0, pre,
+                             5 * H, cp, s.whf, ho, co, ga, s.hb[0]);
+        else
+          hipLaunchKernelGGL((k_tr_lstm_f<h.value, false>), dim3(grid), dim3(256), 0, st, B,
+                             (const void*)s.hb[(t - 1) & 1], pre, 5 * H, cp, s.whf, ho, co, ga, s.hb[t & 1]);
+      });
     }
   } else {
     for (int t = 0; t < T; ++t) {
@@ -1962,32 +1725,17 @@ static void decoder_core(const GemmCtx& gc, const aa_ref_weights* w, const Train
   tgemm(gc, R, P, H, s.Hs, H, 0, w->att_affine_g_w, H, 0, s.PG, PP);
   tgemm(gc, R, P, H, s.S, H, 0, w->att_affine_s_w, H, 0, s.PS, PP);
   if (join) join->to_main();
-  static const bool tra_row = [] {  // AA_TRA_ROW=1: the per-row k_tr_atten (bitwise A/B of the two forms)
-    const char* e = getenv("AA_TRA_ROW");
-    return e && atoi(e) == 1;
-  }();
-  if (tra_row) {
-    hipLaunchKernelGGL(k_tr_atten, dim3(R), dim3(256), 0, st, B, H, s.PG, s.PS, s.VWv, s.V, w->att_affine_h_w, s.Hs,
-                       s.S, s.alpha, s.beta, s.ctx, s.U);
-  } else {
-    // rows grouped by image (V_b read once per group): groups of TS steps so that the grid covers
-    // the chip (>= 256 workgroups when B is small)
-    int G = B > 0 ? (256 + B - 1) / B : 1;
-    G = G < T ? G : T;
-    G = G > (T + TRA_TS - 1) / TRA_TS ? G : (T + TRA_TS - 1) / TRA_TS;  // at most TRA_TS steps per group
-    const int TS = (T + G - 1) / G;
-    G = (T + TS - 1) / TS;
-#define AA_TRA(H_)                                                                                               \
-  hipLaunchKernelGGL(k_tr_atten_img<H_>, dim3(B, G), dim3(H_), 0, st, B, T, TS, s.PG, s.PS, s.VWv, s.V,          \
-                     w->att_affine_h_w, s.Hs, s.S, s.alpha, s.beta, s.ctx, s.U)
-    switch (H) {
-      case 256: AA_TRA(256); break;
-      case 512: AA_TRA(512); break;
-      case 768: AA_TRA(768); break;
-      default: AA_TRA(1024); break;
-    }
-#undef AA_TRA
-  }
+  // rows grouped by image (V_b read once per group): groups of TS steps so that the grid covers
+  // the chip (>= 256 workgroups when B is small)
+  int G = B > 0 ? (256 + B - 1) / B : 1;
+  G = G < T ? G : T;
+  G = G > (T + TRA_TS - 1) / TRA_TS ? G : (T + TRA_TS - 1) / TRA_TS;  // at most TRA_TS steps per group
+  const int TS = (T + G - 1) / G;
+  G = (T + TS - 1) / TS;
+  aa_for_hidden(H, [&](auto h) {
+    hipLaunchKernelGGL(k_tr_atten_img<h.value>, dim3(B, G), dim3(h.value), 0, st, B, T, TS, s.PG, s.PS, s.VWv, s.V,
+                       w->att_affine_h_w, s.Hs, s.S, s.alpha, s.beta, s.ctx, s.U);
+  });
 }
 
 int aa_train_forward(const aa_ref_weights* w, const aa_dims* dims, const float* feats, int32_t B, int32_t T,
@@ -2262,20 +2010,15 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
       const float* cp = t ? s.Cs + o - (size_t)B * H : s.c0;
       const float* ga4 = s.GA + (size_t)t * B * 4 * H;
       float* dg = s.DG + (size_t)t * B * 4 * H;
-#define AA_LB(H_)                                                                                                   \
-  if (t == T - 1)                                                                                                   \
-    hipLaunchKernelGGL((k_tr_lstm_b<H_, true>), dim3(grid), dim3(256), 0, st, B, (const __bf16*)nullptr, s.whb,     \
-                       s.dH + o, s.dC + o, s.dc_rec, ga4, s.Cs + o, cp, dg, s.dgb[t & 1]);                          \
-  else                                                                                                              \
-    hipLaunchKernelGGL((k_tr_lstm_b<H_, false>), dim3(grid), dim3(256), 0, st, B, (const __bf16*)s.dgb[(t + 1) & 1], \
-                       s.whb, s.dH + o, s.dC + o, s.dc_rec, ga4, s.Cs + o, cp, dg, s.dgb[t & 1])
-      switch (H) {
-        case 256: AA_LB(256); break;
-        case 512: AA_LB(512); break;
-        case 768: AA_LB(768); break;
-        default: AA_LB(1024); break;
-      }
-#undef AA_LB
+      aa_for_hidden(H, [&](auto h) {
+        if (t == T - 1)
+          hipLaunchKernelGGL((k_tr_lstm_b<h.value, true>), dim3(grid), dim3(256), 0, st, B, (const __bf16*)nullptr,
+                             s.whb, s.dH + o, s.dC + o, s.dc_rec, ga4, s.Cs + o, cp, dg, s.dgb[t & 1]);
+        else
+          hipLaunchKernelGGL((k_tr_lstm_b<h.value, false>), dim3(grid), dim3(256), 0, st, B,
+                             (const __bf16*)s.dgb[(t + 1) & 1], s.whb, s.dH + o, s.dC + o, s.dc_rec, ga4, s.Cs + o, cp,
+                             dg, s.dgb[t & 1]);
+      });
     }
     f.to_aux();  // DG complete: the LSTM weight gradients on aux
     tgemm(gc, B, H, 4 * H, s.DG, 4 * H, 0, s.whhT, 4 * H, 0, s.dh_rec, H);

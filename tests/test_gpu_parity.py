@@ -194,15 +194,22 @@ def test_decode_plan_replay_equals_sampler(model, gpu_device, exact):
     plan.close()
 
 
-@pytest.mark.parametrize("hidden,B", [(256, 37), (768, 20), (1024, 24)])
-def test_other_hidden_sizes_vs_oracle(gpu_device, hidden, B):
-    """The general-dims kernels: hidden 256 (k_vscreen2 tiles, k_enc_v4<2>), 768 and 1024 (the 64 x 64
-    screen k_vscreen, the 128 x 128-tile encoder k_enc_v3, k_atten<HPT>) against the oracle; the
-    screened ids equal the exact-vocab ids (the screen bound's H-dependent accumulation term,
-    sc_acc(H))."""
-    from adaptive_amd import Config, Encoder2Decoder
+@pytest.mark.parametrize("hidden,B,vocab", [
+    pytest.param(256, 37, 3001, id="256-37"),
+    pytest.param(768, 20, 3001, id="768-20"),
+    pytest.param(1024, 24, 3001, id="1024-24"),
+    pytest.param(256, 37, 3200, id="256-37-3200"),
+])
+def test_other_hidden_sizes_vs_oracle(gpu_device, hidden, B, vocab):
+    """The general-dims kernels against the oracle: hidden 256 (k_enc_v4<2>, k_atten<1>), 768 and 1024
+    (the 128 x 128-tile encoder k_enc_v3, k_atten<HPT>).  Vocab 3001 pads to 3072 rows, no multiple of
+    the wide screen's 160 columns, so every hidden size there runs the 64 x 64 screen k_vscreen; vocab
+    3200 = 20 x 160 puts hidden 256 on the wide screen k_vscreen8<256>, and there AA_DECODE_SCREEN4
+    (k_vscreen2<256>) must give the same ids, alpha and beta bit for bit.  The screened ids equal the
+    exact-vocab ids (the screen bound's H-dependent accumulation term, sc_acc(H))."""
+    from adaptive_amd import Config, Encoder2Decoder, _lib
     from oracle.adaptive_oracle import OracleModel
-    cf = Config(adaptive_word_embed_size=256, adaptive_lstm_hidden_size=hidden, vocab_length=3001)
+    cf = Config(adaptive_word_embed_size=256, adaptive_lstm_hidden_size=hidden, vocab_length=vocab)
     m = Encoder2Decoder(cf).to(gpu_device)
     m.load_synthetic(7)
     feats = synth.make_features(B, seed=29)
@@ -213,6 +220,12 @@ def test_other_hidden_sizes_vs_oracle(gpu_device, hidden, B):
     np.testing.assert_allclose(beta.cpu().numpy(), r_beta.numpy(), atol=ATT_TOL, rtol=0)
     ex = m.sampler(torch.from_numpy(feats).to(gpu_device), max_len=12, exact_vocab=True)
     assert torch.equal(ex[0].cpu(), r_ids)
+    if vocab % 160 == 0:
+        m.decode_extra_flags = _lib.DECODE_SCREEN4
+        s4 = m.sampler(torch.from_numpy(feats).to(gpu_device), max_len=12)
+        m.decode_extra_flags = 0
+        for x, y in zip((ids, alpha, beta), s4):
+            assert torch.equal(x, y)
 
 
 def test_greedy_matches_oracle_odd_batch(model, oracle, gpu_device):

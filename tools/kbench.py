@@ -16,7 +16,7 @@ SO = os.path.join(ROOT, "tools", "_build", "libkbench.so")
 
 
 def main():
-    names = sys.argv[1:] or ["lstm", "atten", "vscreen", "vrescore"]
+    names = sys.argv[1:] or ["lstm", "atten5", "vscreen8", "vrescore"]
     if not os.path.exists(SO):
         os.makedirs(os.path.dirname(SO), exist_ok=True)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
