@@ -18,13 +18,14 @@ import torch  # noqa: F401  (must precede the CDLL: shares torch's HIP runtime)
 # AA_LIB_PATH: load another build of the same library (A/B timing of two builds in one GPU session)
 LIB_PATH = os.environ.get("AA_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                          "libadaptive_amd.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 DECODE_EXACT_VOCAB = 1
 DECODE_FP32_ENCODER = 2
 DECODE_ONE_STREAM = 512
 DECODE_SPLIT_RESCORE = 1024  # rescoring in its own launch per step (cross-check of the fused default)
 DECODE_RS_SELF = 2048  # test hook: fused launch's LSTM workgroups rescore unpublished rows themselves
 DECODE_SCREEN4 = 4096  # vocab screen on k_vscreen2 (4 waves) instead of k_vscreen8: the same summaries
+DECODE_BASELINE = 8192  # baseline (no-sentinel) model: must match how the model was packed
 BEAM_FAST = 256
 TRAIN_BF16 = 128
 MAX_BEAM = 8
@@ -104,6 +105,9 @@ SIGNATURES = {
     "aa_decode_step": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),
+    "aa_baseline_decode_step": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p]),
     "aa_decode_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "aa_greedy_decode": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_size_t, POINTER(Trace), c_int32, c_void_p]),

@@ -191,12 +191,13 @@ class DecodePlan:
             self.images = torch.empty(B, d.channels, 7, 7, dtype=torch.float32, device=dev)
             self.ids = torch.empty(B, T, dtype=torch.int64, device=dev)
             self.alpha = torch.empty(B, T, ATT, dtype=torch.float32, device=dev)
-            self.beta = torch.empty(B, T, 1, dtype=torch.float32, device=dev)
+            # (a baseline model has no sentinel gate: no beta buffer, and the plan returns (ids, alpha))
+            self.beta = None if self.flags & _lib.DECODE_BASELINE else torch.empty(B, T, 1, dtype=torch.float32, device=dev)
             nbytes = lib.aa_decode_workspace_bytes(model._c_dims(), B, T)
             self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             h = ctypes.c_void_p()
             _lib.check(lib.aa_decode_plan_create(mstruct, self.images.data_ptr(), B, T, self.ids.data_ptr(),
-                                                 self.alpha.data_ptr(), self.beta.data_ptr(), self.ws.data_ptr(),
+                                                 self.alpha.data_ptr(), _lib.ptr(self.beta), self.ws.data_ptr(),
                                                  nbytes, self.flags, ctypes.byref(h)), "decode_plan_create")
         self.handle = h
         self._done = None  # completion event of the last replay
@@ -223,6 +224,8 @@ class DecodePlan:
             with torch.cuda.device(self.device), torch.cuda.stream(s):
                 self.images.copy_(images, non_blocking=True)
         self.launch(s)
+        if self.beta is None:
+            return self.ids, self.alpha
         return self.ids, self.alpha, self.beta
 
     def close(self) -> None:
@@ -366,10 +369,14 @@ class Encoder2Decoder(nn.Module):
         d = self.dims
         return _lib.Dims(d.embed, d.hidden, d.vocab, d.channels, d.spatial)
 
+    # (aa_ref_weights field, state-dict key) of the parameters this model has; a field that is
+    # absent here is passed to aa_pack_weights as NULL (baseline_attention.Encoder2Decoder)
+    _weight_fields = _lib.WEIGHT_FIELDS
+
     def _model_struct(self) -> _lib.Model:
         """Pack parameters if any changed since the last pack (data_ptr + version counters)."""
         params = dict(self.named_parameters())
-        names = [k for _, k in _lib.WEIGHT_FIELDS]
+        names = [k for _, k in self._weight_fields]
         dev = params[names[0]].device
         if dev.type != "cuda":
             raise RuntimeError("adaptive_amd.Encoder2Decoder runs on the GPU only: call .cuda() first")
@@ -386,7 +393,7 @@ class Encoder2Decoder(nn.Module):
                 raise RuntimeError(f"adaptive_amd: parameter {n} must be contiguous fp32 on {dev}")
         packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         model = _lib.Model(cd, packed.data_ptr(), nbytes)
-        w = _lib.RefWeights(**{f: params[k].data_ptr() for f, k in _lib.WEIGHT_FIELDS})
+        w = _lib.RefWeights(**{f: params[k].data_ptr() for f, k in self._weight_fields})
         with torch.cuda.device(dev):
             _lib.check(lib.aa_pack_weights(model, w, _lib.stream_handle()), "pack_weights")
         self._packed, self._model, self._pack_key = packed, model, key
@@ -473,7 +480,7 @@ class Encoder2Decoder(nn.Module):
                 aux = self._aux_stream(dev)
                 aux.wait_stream(s)  # (the library forks/joins through events too)
             rc = lib.aa_greedy_decode_aux(model, images.data_ptr(), B, T, ids.data_ptr(), alpha.data_ptr(),
-                                          beta.data_ptr(), _lib.ptr(ws), ws.numel() if ws is not None else 0,
+                                          _lib.ptr(beta), _lib.ptr(ws), ws.numel() if ws is not None else 0,
                                           trace, flags, s.cuda_stream, aux.cuda_stream if aux is not None else None)
         _lib.check(rc, "greedy_decode")
 

@@ -893,7 +893,11 @@ constexpr int LS_CP = 68;  // k_lstm LDS tile pitch (floats): conflict-free cell
 constexpr int LS_HP = 68;    // pitch of the transposed h' / s tiles [unit][row]: conflict-free MFMA A reads
 constexpr int LS_WSP = 100;  // 98 projection outputs padded to whole float4s
 constexpr int LS_TAIL_FLOATS = 2 * 16 * LS_HP + 16 * LS_WSP;
-template <int H>
+// SENT = false (the baseline spatial-attention model, baseline_attention.py:78-128: no sentinel): no
+// s (sa / sb are not read, the Ss tile and the s_out store are gone) and only the W_g half of the
+// projections -- waves 0..3 (cb < 2), columns 0..63 of a part row; c', h', the split-h fragments and
+// the W_g partials by the same arithmetic in the same order as with the sentinel.
+template <int H, bool SENT = true>
 __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const float (&gate)[4][2], float2 sa, float2 sb,
                                                float2 cprev, float4 wsv, float* Hs, float* h_out,
                                                bf16x8* __restrict__ hsp_out, float* __restrict__ c_out,
@@ -905,10 +909,10 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
   const int rr = t >> 3, u0 = (t & 7) * 2, m = m0 + rr, j = nt * 16 + u0;
   {  // transpose the W_g / W_s slice to [unit][j] (j = 98, 99 are zero)
     const int jj = t >> 2, uq = (t & 3) * 4;
-    if (t < 2 * P * 4) {
+    if (t < (SENT ? 2 : 1) * P * 4) {
       Wsl[(uq + 0) * WSP + jj] = wsv.x; Wsl[(uq + 1) * WSP + jj] = wsv.y;
       Wsl[(uq + 2) * WSP + jj] = wsv.z; Wsl[(uq + 3) * WSP + jj] = wsv.w;
-    } else if (t < 2 * P * 4 + 32) {
+    } else if (SENT && t < 2 * P * 4 + 32) {
       const int z = t - 2 * P * 4;  // 32 zeros: j = 98, 99 for 16 units
       Wsl[(z >> 1) * WSP + 2 * P + (z & 1)] = 0.f;
     }
@@ -922,16 +926,18 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
       cn[q] = f_ * (&cprev.x)[q] + i_ * g_;
       const float tc = tanhf(cn[q]);
       hn[q] = o_ * tc;
-      sn[q] = sigmoidf_((&sa.x)[q] + (&sb.x)[q]) * tc;
+      if constexpr (SENT) sn[q] = sigmoidf_((&sa.x)[q] + (&sb.x)[q]) * tc;
     }
     Hs[u0 * HP + rr] = hn[0];
     Hs[(u0 + 1) * HP + rr] = hn[1];
-    Ss[u0 * HP + rr] = sn[0];
-    Ss[(u0 + 1) * HP + rr] = sn[1];
+    if constexpr (SENT) {
+      Ss[u0 * HP + rr] = sn[0];
+      Ss[(u0 + 1) * HP + rr] = sn[1];
+    }
     if (m < B) {
       st_wt(reinterpret_cast<float2*>(c_out + (int64_t)m * H + j), make_float2(cn[0], cn[1]));
       st_wt(reinterpret_cast<float2*>(h_out + (int64_t)m * H + j), make_float2(hn[0], hn[1]));
-      st_wt(reinterpret_cast<float2*>(s_out + (int64_t)m * H + j), make_float2(sn[0], sn[1]));
+      if constexpr (SENT) st_wt(reinterpret_cast<float2*>(s_out + (int64_t)m * H + j), make_float2(sn[0], sn[1]));
       if (hsp_out) {
         // next step's A fragments: k = j.. in chunk nt, lane (m % 32) + 32 * (u0 / 8), elements u0 % 8..
         typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -953,7 +959,7 @@ __device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const floa
   AA_TS(0, 3);
   __syncthreads();
   // Wave -> one 32x32 block: rows rb*32.., columns cb = 0, 1: W_g j = 0..63; cb = 2, 3: W_s j = 0..63.
-  {
+  if (SENT || wave < 4) {
     const int rb = wave & 1, cb = wave >> 1, li = lane & 31, lh = lane >> 5;
     const float* X = cb < 2 ? Hs : Ss;
     const int jj = (cb & 1) * 32 + li, jg = (cb < 2 ? 0 : P) + jj, jgc = jg < WSP ? jg : WSP - 1;
@@ -1149,7 +1155,10 @@ __device__ __forceinline__ uint64_t rescore_row(int b, bool write, int t, int V,
 constexpr uint64_t RS_WAIT_TICKS = 5000;  // 50 us of the 100 MHz constant clock
 // ring iterations (of H / 32) at which k_lstm<.., RS> DMAs the tile's keys and gathers the table rows
 constexpr int LS_RS_JK = 10, LS_RS_JG = LS_RS_JK + 3;
-template <int H, bool G = false, bool RS = false>
+// SENT = false: the baseline model's step -- the sentinel's x W_x^T gathers (sa, sb) are not issued,
+// so the gathers are LS_GATHERS - 2 ordinary loads (the ring's counted waits are told so), and the
+// cell tail is lstm_cell_tail<H, false>; s_out is not written.
+template <int H, bool G = false, bool RS = false, bool SENT = true>
 __global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __restrict__ tok, int tok_ld,
                                               const float* __restrict__ table,
                                               const float* __restrict__ xg, const bf16x8* __restrict__ hsp_in,
@@ -1222,6 +1231,9 @@ __global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __
   const bf16x8* wf1 = wf0 + (size_t)KC * 3 * 64;
   // epilogue gathers behind the first GEMM loads: token -> table row, x_g, c, W_g/W_s slice
   float2 ta[4], xa[4], sa, sb, cprev;
+  if constexpr (!SENT) sa = sb = make_float2(0.f, 0.f);  // (not gathered, not read)
+  constexpr int NGATH = SENT ? LS_GATHERS : LS_GATHERS - 2;  // ordinary loads of gathers()
+  constexpr int NWS4 = (SENT ? 2 : 1) * P * 4;               // float4s of the tile's W_g (/ W_s) slice in use
   float4 wsv;
   const int N5 = 5 * H;
   // the token's table row (5 loads)
@@ -1230,18 +1242,18 @@ __global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __
     const float* trow = table + tk * N5;
 #pragma unroll
     for (int g = 0; g < 4; ++g) ta[g] = *reinterpret_cast<const float2*>(trow + nt * 64 + g * 16 + u0);
-    sa = *reinterpret_cast<const float2*>(trow + 4 * H + j);
+    if constexpr (SENT) sa = *reinterpret_cast<const float2*>(trow + 4 * H + j);
   };
   // the token-independent operands: x_g, c, the W_g / W_s slice (7 loads)
   auto gather_x = [&] {
     const float* xrow = xg + (int64_t)mc * N5;
 #pragma unroll
     for (int g = 0; g < 4; ++g) xa[g] = *reinterpret_cast<const float2*>(xrow + nt * 64 + g * 16 + u0);
-    sb = *reinterpret_cast<const float2*>(xrow + 4 * H + j);
+    if constexpr (SENT) sb = *reinterpret_cast<const float2*>(xrow + 4 * H + j);
     cprev = *reinterpret_cast<const float2*>(c_in + (int64_t)pc * H + j);
     // W_g / W_s slice: wgs[tile] is [98][16] (j-major); thread t < 392 takes float4 t
     const float4* src = reinterpret_cast<const float4*>(wgs + (int64_t)nt * 2 * P * 16);
-    wsv = src[t < 2 * P * 4 ? t : 2 * P * 4 - 1];
+    wsv = src[t < NWS4 ? t : NWS4 - 1];
   };
   auto gathers = [&] {
     gather_table();
@@ -1262,7 +1274,7 @@ __global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __
     uint32_t* klo = reinterpret_cast<uint32_t*>(lds + RING_FLOATS + 64 + 4);
     // (hooks scaled to the ring's H / 32 iterations; rings under 12 iterations: gathers after the ring)
     constexpr int NI = H / 32, JK = NI >= 12 ? LS_RS_JK * NI / 16 : -1, JG = JK < 0 ? -1 : JK + (LS_RS_JG - LS_RS_JK);
-    lstm_gemm_lds<H, 0, JK, JG, 12>(
+    lstm_gemm_lds<H, 0, JK, JG, NGATH>(
         af0, af1, wf0, wf1, reinterpret_cast<bf16x8*>(lds), Pt, [] {},
         [&] {
           if (t < 64) {
@@ -1320,7 +1332,7 @@ __global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __
       gathers();
     }
   } else {
-    lstm_gemm_lds<H>(af0, af1, wf0, wf1, reinterpret_cast<bf16x8*>(lds), Pt, [&] {
+    lstm_gemm_lds<H, NGATH>(af0, af1, wf0, wf1, reinterpret_cast<bf16x8*>(lds), Pt, [&] {
       // wave 0's token DMA is older than its ring DMAs: retire it, then every wave reads its row's
       if (t < 64) vm_wait(LS_NPW * (LS_NB < H / 32 ? LS_NB : H / 32));
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1340,7 +1352,7 @@ __global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __
       for (int q = 0; q < 2; ++q) gate[g][q] = cr[(16 * g + u0 + q) * CP] + ((&ta[g].x)[q] + (&xa[g].x)[q]);
   }
   AA_TS(0, 2);
-  lstm_cell_tail<H>(B, m0, nt, gate, sa, sb, cprev, wsv, lds + TS, h_out, hsp_out, c_out, s_out, part);
+  lstm_cell_tail<H, SENT>(B, m0, nt, gate, sa, sb, cprev, wsv, lds + TS, h_out, hsp_out, c_out, s_out, part);
   AA_TS(0, 4);
 }
 
@@ -1547,7 +1559,10 @@ struct AttSmem {
   float norm[16];
   float beta;
 };
-template <int H, class VG>
+// SENT = false (the baseline model, baseline_attention.py:78-96,126): only the 49 W_g projections are
+// summed, 49 scores, one softmax, u = c_t + h; sv and beta_out are not touched.  alpha comes out of
+// the same operations in the same order as with the sentinel (beta does not enter alpha).
+template <int H, bool SENT = true, class VG>
 __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H / 64], const float (&vwr)[7],
                                                const float (&whr)[7], const float (&hv)[H / 512],
                                                const float (&sv)[H / 512], VG&& vget, AttSmem& sm,
@@ -1567,7 +1582,7 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
   }
   __syncthreads();
   AA_TS(1, 1);
-  if (t < 2 * P) sm.proj[t] = (sm.red[0][t] + sm.red[1][t]) + (sm.red[2][t] + sm.red[3][t]);
+  if (t < (SENT ? 2 : 1) * P) sm.proj[t] = (sm.red[0][t] + sm.red[1][t]) + (sm.red[2][t] + sm.red[3][t]);
   __syncthreads();
   // 2) scores: item k (0..49) by 8 lanes, j = q + 8i
   {
@@ -1575,20 +1590,22 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       const int j = q + 8 * i < P ? q + 8 * i : P - 1;
-      const float x = (k < P ? vwr[i] : sm.proj[P + j]) + sm.proj[j];
+      float x;
+      if constexpr (SENT) x = (k < P ? vwr[i] : sm.proj[P + j]) + sm.proj[j];
+      else x = vwr[i] + sm.proj[j];
       z = __builtin_fmaf(whr[i], tanhf(x), z);
     }
     z = z + __shfl_xor(z, 1, 64);
     z = z + __shfl_xor(z, 2, 64);
     z = z + __shfl_xor(z, 4, 64);
-    if (q == 0 && k <= P) sm.zs[k] = z;
+    if (q == 0 && k < P + (SENT ? 1 : 0)) sm.zs[k] = z;
   }
   __syncthreads();
   AA_TS(1, 2);
   // 3) softmax (wave 0)
   if (w == 0) {
     const float z = lane < P ? sm.zs[lane] : -INFINITY;
-    const float zsn = sm.zs[P];
+    const float zsn = SENT ? sm.zs[P] : 0.f;
     const float m = wave_max(z);
     const float e = lane < P ? expf(z - m) : 0.f;
     const float S = wave_sum(e);
@@ -1597,20 +1614,22 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
       sm.alpha[lane] = a;
       if (alpha_out) alpha_out[(int64_t)b * alpha_ld + lane] = a;
     }
-    const float m2 = fmaxf(m, zsn);
-    const float e2 = lane < P ? expf(z - m2) : 0.f;
-    const float es = expf(zsn - m2);
-    const float S2 = wave_sum(e2) + es;
-    if (lane == 0) {
-      const float beta = es / S2;
-      sm.beta = beta;
-      if (beta_out) beta_out[(int64_t)b * beta_ld] = beta;
+    if constexpr (SENT) {
+      const float m2 = fmaxf(m, zsn);
+      const float e2 = lane < P ? expf(z - m2) : 0.f;
+      const float es = expf(zsn - m2);
+      const float S2 = wave_sum(e2) + es;
+      if (lane == 0) {
+        const float beta = es / S2;
+        sm.beta = beta;
+        if (beta_out) beta_out[(int64_t)b * beta_ld] = beta;
+      }
     }
   }
   __syncthreads();
   AA_TS(1, 3);
   // 4) context + u
-  const float beta = sm.beta;
+  const float beta = SENT ? sm.beta : 0.f;
   float nsq = 0.f, dsq = 0.f;  // ||u||^2 and ||u - bf16(u)||^2 (the screen's bound)
 #pragma unroll
   for (int i = 0; i < DPT; ++i) {
@@ -1618,7 +1637,8 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
     float c = 0.f;
 #pragma unroll
     for (int kk = 0; kk < P; ++kk) c = __builtin_fmaf(sm.alpha[kk], vget(i, kk), c);
-    const float chat = __builtin_fmaf(beta, sv[i], (1.f - beta) * c);
+    float chat = c;  // (no sentinel: c_hat = c_t, baseline_attention.py:122)
+    if constexpr (SENT) chat = __builtin_fmaf(beta, sv[i], (1.f - beta) * c);
     const float u = chat + hv[i];
     nsq = __builtin_fmaf(u, u, nsq);
     u_out[(int64_t)b * H + d] = u;
@@ -1660,7 +1680,9 @@ __device__ __forceinline__ void atten_row_math(int B, int b, const float (&pv)[H
 // flight per CU), the 32 projection partials summed by four groups of 128 threads (8 each, then
 // (g0 + g1) + (g2 + g3)), and each of the 50 scores by 8 lanes (7 terms each, xor-butterfly
 // combine).  Same outputs as k_atten; rounding of the projections / scores differs (fixed orders).
-template <int H>
+// SENT = false: the baseline model's row (atten_row_math<H, false>): the 49 W_g partial columns only,
+// s_new and beta_out are not read / written.
+template <int H, bool SENT = true>
 __global__ __launch_bounds__(512) void k_atten5(int B, int kdiv, const float* __restrict__ h_new,
                                                 const float* __restrict__ s_new, const float* __restrict__ part,
                                                 const float* __restrict__ Vf, const float* __restrict__ VWv,
@@ -1675,7 +1697,8 @@ __global__ __launch_bounds__(512) void k_atten5(int B, int kdiv, const float* __
   const int b = blockIdx.x;
   const int img = kdiv == 1 ? b : b / kdiv;
   // loads, oldest first in the order they are consumed; clamped addresses, no branches
-  const int grp = t >> 7, jp = t & 127, jpc = part_col(jp < 2 * P ? jp : 2 * P - 1);
+  constexpr int NPJ = (SENT ? 2 : 1) * P;  // projection outputs in use
+  const int grp = t >> 7, jp = t & 127, jpc = part_col(jp < NPJ ? jp : NPJ - 1);
   float pv[NG];
   {
     const float* pp = part + ((int64_t)b * NT16 + grp) * PART + jpc;
@@ -1704,10 +1727,11 @@ __global__ __launch_bounds__(512) void k_atten5(int B, int kdiv, const float* __
 #pragma unroll
   for (int i = 0; i < DPT; ++i) {
     hv[i] = h_new[(int64_t)b * H + t + 512 * i];
-    sv[i] = s_new[(int64_t)b * H + t + 512 * i];
+    if constexpr (SENT) sv[i] = s_new[(int64_t)b * H + t + 512 * i];
+    else sv[i] = 0.f;
   }
-  atten_row_math<H>(B, b, pv, vwr, whr, hv, sv, [&](int i, int kk) { return vv[i][kk]; }, sm, alpha_out, alpha_ld,
-                       beta_out, beta_ld, u_out, ub_out, unorm, ub3_out);
+  atten_row_math<H, SENT>(B, b, pv, vwr, whr, hv, sv, [&](int i, int kk) { return vv[i][kk]; }, sm, alpha_out,
+                          alpha_ld, beta_out, beta_ld, u_out, ub_out, unorm, ub3_out);
 }
 
 // k_atten5 for beam search: one workgroup per IMAGE runs the KB rows (beams) of that image, so the
@@ -2557,7 +2581,7 @@ __global__ void k_pack_lstm(const float* __restrict__ w_ih, const float* __restr
     }
     for (int k = threadIdx.x; k < H; k += blockDim.x) whh[(int64_t)r * H + k] = w_hh[(int64_t)src * H + k];
     if (threadIdx.x == 0) bias5[r] = b_ih[src] + b_hh[src];
-  } else {
+  } else if (w_x) {  // (a baseline model has no sentinel: its fifth block stays zero)
     const int j = r - 4 * H;
     for (int k = threadIdx.x; k < E; k += blockDim.x) {
       wemb[(int64_t)r * E + k] = w_x[(int64_t)j * KX + k];
@@ -2606,7 +2630,8 @@ __global__ void k_pack_w4(const float* __restrict__ w, int C, bf16x8* __restrict
 
 __global__ void k_pack_wgs(const float* __restrict__ wg, const float* __restrict__ ws, int H, float* __restrict__ out) {
   const int tile = blockIdx.x;
-  for (int i = threadIdx.x; i < 2 * P * 16; i += blockDim.x) {
+  // (ws == nullptr: a baseline model, the W_s half stays zero)
+  for (int i = threadIdx.x; i < (ws ? 2 : 1) * P * 16; i += blockDim.x) {
     const int j = i / 16, u = i % 16;
     const float* src = j < P ? wg + (int64_t)j * H : ws + (int64_t)(j - P) * H;
     out[(int64_t)tile * 2 * P * 16 + i] = src[tile * 16 + u];
@@ -2725,10 +2750,13 @@ int aa_pack_weights(const aa_model* m, const aa_ref_weights* w, aa_stream_t stre
   const float* req[] = {w->enc_affine_a_w, w->enc_affine_a_b, w->enc_affine_b_w, w->enc_affine_b_b,
                         w->enc_affine_h0_w, w->enc_affine_h0_b, w->enc_affine_c0_w, w->enc_affine_c0_b,
                         w->embed_w, w->lstm_w_ih, w->lstm_w_hh, w->lstm_b_ih, w->lstm_b_hh,
-                        w->sent_affine_x_w, w->att_affine_v_w, w->att_affine_g_w, w->att_affine_s_w,
-                        w->att_affine_h_w, w->mlp_w, w->mlp_b};
+                        w->att_affine_v_w, w->att_affine_g_w, w->att_affine_h_w, w->mlp_w, w->mlp_b};
   for (const float* p : req)
     if (!p) return AA_ERR_NULL;
+  // both sentinel weights NULL: a baseline (no-sentinel) model, whose sentinel blocks stay zero; one
+  // without the other is an error
+  const bool baseline = !w->sent_affine_x_w && !w->att_affine_s_w;
+  if (!baseline && (!w->sent_affine_x_w || !w->att_affine_s_w)) return AA_ERR_NULL;
   if (!al16(w->embed_w)) return AA_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   float* base = static_cast<float*>(m->packed);
@@ -2747,7 +2775,7 @@ int aa_pack_weights(const aa_model* m, const aa_ref_weights* w, aa_stream_t stre
   AA_TRY(cp(w->enc_affine_c0_b, L.heads_b + E + H, H));
   AA_TRY(cp(w->att_affine_v_w, L.wv, (size_t)P * H));  // rows 49..63 stay zero
   AA_TRY(cp(w->att_affine_g_w, L.wg, (size_t)P * H));
-  AA_TRY(cp(w->att_affine_s_w, L.ws, (size_t)P * H));
+  if (!baseline) AA_TRY(cp(w->att_affine_s_w, L.ws, (size_t)P * H));
   AA_TRY(cp(w->att_affine_h_w, L.wh, P));
   AA_TRY(cp(w->mlp_w, L.mlp_w, (size_t)V * H));        // rows V..Vp-1 stay zero
   AA_TRY(cp(w->mlp_b, L.mlp_b, V));
@@ -3032,10 +3060,20 @@ size_t aa_decode_workspace_bytes(const aa_dims* d, int32_t B, int32_t T) {
 static void lstm_launch(const Layout& L, const MP& p, int B, const int64_t* tok, int tok_ld, const float* xg,
                         const bf16x8* hsp_in, const float* c_in, float* h_out, bf16x8* hsp_out, float* c_out,
                         float* s_buf, float* part, hipStream_t s, const int* par = nullptr,
-                        const RsArgs* ra = nullptr, aa_event_t* ev = nullptr, int ei = 0) {
+                        const RsArgs* ra = nullptr, aa_event_t* ev = nullptr, int ei = 0, bool base = false) {
   const int H = L.H, MT = (B + 63) / 64;
   const RsArgs none{};
   const int64_t* tnull = nullptr;
+  if (base) {  // the baseline model's no-sentinel step (H = 512, greedy: baseline_ok()); s_buf is not written
+    if (ra)
+      AA_TLAUNCH(ev, ei, (k_lstm<512, false, true, false>), dim3(ra->NR + MT * (512 / 16)), dim3(512), 0, s, B, L.V,
+                 tnull, 0, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part,
+                 *ra);
+    else
+      AA_TLAUNCH(ev, ei, (k_lstm<512, false, false, false>), dim3(MT * (512 / 16)), dim3(512), 0, s, B, L.V, tok,
+                 tok_ld, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);
+    return;
+  }
   aa_for_hidden(H, [&](auto h) {
     constexpr int H_ = h.value;
     if (par)
@@ -3055,10 +3093,15 @@ static void lstm_launch(const Layout& L, const MP& p, int B, const int64_t* tok,
 static void atten_launch(const Layout& L, const MP& p, int B, const float* V, const float* vwv, const float* h_out,
                          float* s_buf, float* part, float* u, uint16_t* ub, float* unorm, float* alpha,
                          int64_t alpha_ld, float* beta, int64_t beta_ld, hipStream_t s, int kdiv = 1,
-                         bf16x8* ub3 = nullptr, aa_event_t* ev = nullptr, int ei = 0) {
+                         bf16x8* ub3 = nullptr, aa_event_t* ev = nullptr, int ei = 0, bool base = false) {
   const int H = L.H;
   const float* sb = s_buf;
   const float* pt = part;
+  if (base) {  // the baseline model's row (H = 512, one row per image): s_buf and beta are not touched
+    AA_TLAUNCH(ev, ei, (k_atten5<512, false>), dim3(B), dim3(512), 0, s, B, kdiv, h_out, sb, pt, V, vwv, p.wh, alpha,
+               alpha_ld, (float*)nullptr, beta_ld, u, ub, unorm, ub3);
+    return;
+  }
 #define AA_ATTEN(HPT_)                                                                                     \
   AA_TLAUNCH(ev, ei, k_atten<HPT_>, dim3(B), dim3(256), 0, s, B, H / 16, kdiv, h_out, sb, pt, V, vwv, p.wh, alpha, \
              alpha_ld, beta, beta_ld, u, ub, unorm, ub3)
@@ -3094,20 +3137,25 @@ static void lstm_atten_launch(const Layout& L, const MP& p, int B, const int64_t
                               const float* c_in, float* h_out, bf16x8* hsp_out, float* c_out, float* s_buf, float* part, float* u, uint16_t* ub,
                               float* unorm, float* alpha, int64_t alpha_ld, float* beta, int64_t beta_ld,
                               const aa_trace* tr, int t, hipStream_t s, const int* par = nullptr, int kdiv = 1,
-                              bf16x8* ub3 = nullptr, const RsArgs* ra = nullptr) {
+                              bf16x8* ub3 = nullptr, const RsArgs* ra = nullptr, bool base = false) {
   lstm_launch(L, p, B, tok, tok_ld, xg, hsp_in, c_in, h_out, hsp_out, c_out, s_buf, part, s, par, ra,
-              tr ? tr->lstm_events : nullptr, 2 * t);
+              tr ? tr->lstm_events : nullptr, 2 * t, base);
   atten_launch(L, p, B, V, vwv, h_out, s_buf, part, u, ub, unorm, alpha, alpha_ld, beta, beta_ld, s, kdiv, ub3,
-               tr ? tr->atten_events : nullptr, 2 * t);
+               tr ? tr->atten_events : nullptr, 2 * t, base);
 }
 
-int aa_decode_step(const aa_model* m, int32_t B, const int64_t* tokens_in, const float* V, const float* VWv,
-                   const float* v_g, const float* h_in, const float* c_in, float* h_out, float* c_out, float* scores,
-                   int64_t* tokens_out, float* alpha, float* beta, void* workspace, size_t workspace_bytes,
-                   aa_stream_t stream) {
+// The no-sentinel kernels exist for the reference's base_lstm_hidden_size only (k_atten5<512>'s path).
+static bool baseline_ok(const Layout& L) { return L.H == 512; }
+
+// aa_decode_step / aa_baseline_decode_step (base: the no-sentinel kernels, beta unused)
+static int step_impl(const aa_model* m, int32_t B, const int64_t* tokens_in, const float* V, const float* VWv,
+                     const float* v_g, const float* h_in, const float* c_in, float* h_out, float* c_out, float* scores,
+                     int64_t* tokens_out, float* alpha, float* beta, void* workspace, size_t workspace_bytes,
+                     aa_stream_t stream, bool base) {
   Layout L;
   int rc = check_model(m, &L);
   if (rc) return rc;
+  if (base && !baseline_ok(L)) return AA_ERR_DIMS;
   if (B < 0) return AA_ERR_SHAPE;
   if (B == 0) return AA_OK;
   if (!V || !v_g || !h_in || !c_in || !h_out || !c_out || !tokens_out || !workspace) return AA_ERR_NULL;
@@ -3133,11 +3181,27 @@ int aa_decode_step(const aa_model* m, int32_t B, const int64_t* tokens_in, const
     tok = w.tok0;
   }
   lstm_atten_launch(L, p, B, tok, 1, V, VWv, w.xg, w.hsp, c_in, h_out, nullptr, c_out, w.s, w.part, w.u,
-                    nullptr, nullptr, alpha, P, beta, 1, nullptr, 0, s);
+                    nullptr, nullptr, alpha, P, beta, 1, nullptr, 0, s, nullptr, 1, nullptr, nullptr, base);
   hipLaunchKernelGGL(k_vocab, dim3(((B + 63) / 64) * (L.Vp / 64)), dim3(256), 0, s, B, L.H, L.V, L.Vp, L.V, w.u, p.mlp_w,
                      p.mlp_b, scores, w.keys);
   hipLaunchKernelGGL(k_finalize, dim3((B + 255) / 256), dim3(256), 0, s, w.keys, B, 1, tokens_out, B);
   return launch_status();
+}
+
+int aa_decode_step(const aa_model* m, int32_t B, const int64_t* tokens_in, const float* V, const float* VWv,
+                   const float* v_g, const float* h_in, const float* c_in, float* h_out, float* c_out, float* scores,
+                   int64_t* tokens_out, float* alpha, float* beta, void* workspace, size_t workspace_bytes,
+                   aa_stream_t stream) {
+  return step_impl(m, B, tokens_in, V, VWv, v_g, h_in, c_in, h_out, c_out, scores, tokens_out, alpha, beta, workspace,
+                   workspace_bytes, stream, false);
+}
+
+int aa_baseline_decode_step(const aa_model* m, int32_t B, const int64_t* tokens_in, const float* V, const float* VWv,
+                            const float* v_g, const float* h_in, const float* c_in, float* h_out, float* c_out,
+                            float* scores, int64_t* tokens_out, float* alpha, void* workspace, size_t workspace_bytes,
+                            aa_stream_t stream) {
+  return step_impl(m, B, tokens_in, V, VWv, v_g, h_in, c_in, h_out, c_out, scores, tokens_out, alpha, nullptr,
+                   workspace, workspace_bytes, stream, true);
 }
 
 // wide vocab-screen tiles (k_vscreen2) when the padded vocabulary is whole 160-column tiles
@@ -3150,6 +3214,7 @@ static bool screen_wide(const Layout& L) { return L.Vp % SC2_BN == 0 && L.H <= 5
 static int decode_rows(const Layout& L, const MP& p, const DecodeWS& w, int B, int T, int32_t flags, int64_t* ids,
                        float* alpha, float* beta, const aa_trace* trace, hipStream_t s) {
   const bool exact = (flags & AA_DECODE_EXACT_VOCAB) != 0;
+  const bool base = (flags & AA_DECODE_BASELINE) != 0;  // no-sentinel kernels; beta is not touched
   const int H = L.H, MT = (B + 63) / 64;
   const bool wide = screen_wide(L);
   // the rescoring of step t-1 rides in step t's LSTM launch (k_lstm<.., RS>); the last step's has
@@ -3166,9 +3231,9 @@ static int decode_rows(const Layout& L, const MP& p, const DecodeWS& w, int B, i
     RsArgs ra{rup((B + 1) / 2, 8), L.Vp, T, t - 1, (flags & AA_DECODE_RS_SELF) ? 0 : RS_WAIT_TICKS, w.u, w.summ,
               p.mlp_w, p.mlp_b, kt - B, ids};
     lstm_launch(L, p, B, tok, tok_ld, w.xg, w.hsp[cur], w.c[cur], w.h[nxt], w.hsp[nxt], w.c[nxt], w.s, w.part, s,
-                nullptr, fused && t > 0 ? &ra : nullptr, trace ? trace->lstm_events : nullptr, 2 * t);
+                nullptr, fused && t > 0 ? &ra : nullptr, trace ? trace->lstm_events : nullptr, 2 * t, base);
     atten_launch(L, p, B, w.V, w.vwv, w.h[nxt], w.s, w.part, w.u, exact ? nullptr : w.ub, exact ? nullptr : w.unorm,
-                 alt, (int64_t)T * P, blt, T, s, 1, nullptr, trace ? trace->atten_events : nullptr, 2 * t);
+                 alt, (int64_t)T * P, blt, T, s, 1, nullptr, trace ? trace->atten_events : nullptr, 2 * t, base);
     aa_event_t* sev = trace ? trace->screen_events : nullptr;
     aa_event_t* rev = trace ? trace->rescore_events : nullptr;
     if (exact) {
@@ -3214,6 +3279,7 @@ static int greedy_impl(const aa_model* m, const float* feats, int32_t B, int32_t
   Layout L;
   int rc = check_model(m, &L);
   if (rc) return rc;
+  if ((flags & AA_DECODE_BASELINE) && !baseline_ok(L)) return AA_ERR_DIMS;
   if (B < 0 || T < 0) return AA_ERR_SHAPE;
   if (B == 0 || T == 0) return AA_OK;
   if (!feats || !ids || !workspace) return AA_ERR_NULL;
@@ -3269,6 +3335,7 @@ int aa_decode_plan_create(const aa_model* m, const float* feats, int32_t B, int3
   Layout L;
   int rc = check_model(m, &L);
   if (rc) return rc;
+  if ((flags & AA_DECODE_BASELINE) && !baseline_ok(L)) return AA_ERR_DIMS;
   if (B <= 0 || T <= 0) return AA_ERR_SHAPE;
   if (!feats || !ids || !workspace) return AA_ERR_NULL;
   if (!al16(feats) || !al16(workspace)) return AA_ERR_ALIGN;

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AA_ABI_VERSION 16
+#define AA_ABI_VERSION 17
 #define AA_API __attribute__((visibility("default")))
 
 /* error codes (negative); positive codes are hipError_t values */
@@ -148,7 +148,13 @@ AA_API size_t aa_packed_bytes(const aa_dims* dims);
 
 /* Pack reference-layout weights into m->packed (device-side reorder; async on `stream`).
  * Replaces: the parameter set built by Encoder2Decoder.__init__ / load_state_dict
- * (adaptive_attention.py:159-165, model_factory.py:16). */
+ * (adaptive_attention.py:159-165, model_factory.py:16).
+ * Baseline model (baseline_attention.py:198-204, no visual sentinel): sent_affine_x_w and
+ * att_affine_s_w both NULL (sent_affine_h_w too, it is never read).  The packed size and layout are
+ * those of an adaptive model; the sentinel blocks stay zero.  One of the pair NULL without the other
+ * is AA_ERR_NULL.  A model packed this way must be decoded with AA_DECODE_BASELINE /
+ * aa_baseline_decode_step, an adaptive one without: nothing in the packed buffer records which it
+ * is, and the wrong choice computes garbage silently. */
 AA_API int aa_pack_weights(const aa_model* m, const aa_ref_weights* w, aa_stream_t stream);
 
 /* Encoder tail: a_g = AvgPool2d(7)(A); V = relu(A^T W_a^T + b_a); v_g = relu(a_g W_b^T + b_b);
@@ -175,6 +181,17 @@ AA_API int aa_decode_step(const aa_model* m, int32_t B, const int64_t* tokens_in
                           float* alpha, float* beta, void* workspace, size_t workspace_bytes,
                           aa_stream_t stream);
 
+/* aa_decode_step for a baseline-packed model (see aa_pack_weights): Decoder.forward with T == 1
+ * (baseline_attention.py:148-194) through the baseline AdaptiveBlock (:116-128) -- alpha = the
+ * 49-way softmax, scores = mlp(c_t + h) -- and the argmax of its sampler (:267), on the no-sentinel
+ * kernels.  Arguments as aa_decode_step without beta; workspace from aa_step_workspace_bytes.
+ * hidden == 512 only (else AA_ERR_DIMS). */
+AA_API int aa_baseline_decode_step(const aa_model* m, int32_t B, const int64_t* tokens_in,
+                                   const float* V, const float* VWv, const float* v_g,
+                                   const float* h_in, const float* c_in, float* h_out, float* c_out,
+                                   float* scores, int64_t* tokens_out, float* alpha, void* workspace,
+                                   size_t workspace_bytes, aa_stream_t stream);
+
 /* Workspace for aa_greedy_decode at batch B and T steps. */
 AA_API size_t aa_decode_workspace_bytes(const aa_dims* dims, int32_t B, int32_t T);
 
@@ -192,6 +209,14 @@ AA_API size_t aa_decode_workspace_bytes(const aa_dims* dims, int32_t B, int32_t 
                                   (the fallback that keeps the fused launch deadlock-free); same ids */
 #define AA_DECODE_SCREEN4 4096 /* the vocab screen on four waves per 128 x 160 tile (k_vscreen2) instead
                                   of eight (k_vscreen8); the same summaries bit for bit (cross-check) */
+#define AA_DECODE_BASELINE 8192 /* the model is a baseline (no-sentinel) model, packed with
+                                   sent_affine_x_w == att_affine_s_w == NULL: the decode is
+                                   baseline_attention.py's sampler (:233-280) on the no-sentinel kernels;
+                                   beta is neither read nor written (pass NULL); workspace size and layout
+                                   unchanged; hidden == 512 only (else AA_ERR_DIMS); composes with every
+                                   flag above.  The flag MUST match how the model was packed: a
+                                   baseline-packed model decoded without it (or an adaptive one with it)
+                                   computes garbage silently. */
 
 /* Whole greedy decode = Encoder2Decoder.sampler(images, max_len=T) (adaptive_attention.py:168-216,
  * with the baseline's states transpose, baseline_attention.py:251-252).  feats [B,C,7,7];
