@@ -10,6 +10,8 @@ Mirrors the reference module tree and public surface so callers (``code_src/tool
 * ``.decoder(V, v_g, captions, states)`` — Decoder.forward, baseline_attention.py:148-194
   (-> scores, alpha, beta, states): one-token captions run the sampling step, whole captions [B,T]
   the teacher-forced recurrence
+* ``.beam_search(images, ...)`` / ``.sample(images, ...)`` — not in the reference: beam search and
+  seeded temperature sampling over the same decoder step (semantics in include/adaptive_amd.h)
 * state-dict keys identical to the reference (``encoder.affine_a.weight``, ``decoder.LSTM.*``,
   ``decoder.adaptive.{sentinel,atten,mlp}.*``).
 
@@ -555,6 +557,55 @@ class Encoder2Decoder(nn.Module):
                                     vocab_events)
         _lib.check(rc, "beam_decode")
         return ids, alpha, beta, seqs, scores
+
+    @torch.no_grad()
+    def sample(self, images: torch.Tensor, max_len: int = 20, temperature: float = 1.0, seed: int = 0,
+               row0: int = 0, select_events=None):
+        """Seeded temperature-sampling decode (not in the reference; semantics in
+        include/adaptive_amd.h and DESIGN.md) -> (ids [B,T] int64, logp [B,T], alpha [B,T,49],
+        beta [B,T,1]).  Each step draws the next token from softmax(logits / temperature) by
+        Gumbel-max over the exact fp32 logits, with counter-based noise keyed by
+        ``synth.stream_key(seed, "sample")`` and the element ``((row0 + b) T + t) V + v``; ``logp`` is
+        the drawn token's log-probability under the tempered softmax.  All ``max_len`` steps run (no
+        ``<end>`` handling: cut at ``<end>`` as for ``sampler``).  The same ``(seed, row0, max_len)``
+        gives the same output bit for bit, and an image's draw depends only on its global row
+        ``row0 + b``: rows 5..8 of a batch equal a call on those images with ``row0=5``.
+        ``select_events``: address of 2 * max_len raw hipEvent handles
+        (adaptive_amd.hip_events.EventArray.ptr), a pair per step's selection launch."""
+        import math
+        T, tau, seed, row0 = int(max_len), float(temperature), int(seed), int(row0)
+        with np.errstate(over="ignore", under="ignore"):
+            tau32 = float(np.float32(tau))  # the value the kernel divides by
+        if not (math.isfinite(tau) and math.isfinite(tau32) and tau32 > 0.0):
+            raise ValueError(f"temperature must be finite and > 0 (as fp32), got {temperature}")
+        if not 0 <= seed < (1 << 63):
+            raise ValueError(f"seed must be in [0, 2**63), got {seed}")
+        if row0 < 0:
+            raise ValueError(f"row0 must be >= 0, got {row0}")
+        if T < 0:
+            raise ValueError(f"max_len must be >= 0, got {max_len}")
+        from .synth import stream_key
+        images = self._check_images(self.features(images))
+        B, dev = images.size(0), images.device
+        ids = torch.empty(B, T, dtype=torch.int64, device=dev)
+        logp = torch.empty(B, T, dtype=torch.float32, device=dev)
+        alpha = torch.empty(B, T, ATT, dtype=torch.float32, device=dev)
+        beta = torch.empty(B, T, 1, dtype=torch.float32, device=dev)
+        if B == 0 or T == 0:
+            return ids, logp, alpha, beta
+        model = self._model_struct()
+        lib = _lib.load()
+        nbytes = lib.aa_sample_workspace_bytes(self._c_dims(), B, T)
+        if nbytes == 0:
+            raise ValueError(f"unsupported sampling configuration B={B} T={T} for {self.dims}")
+        ws = self._workspace(nbytes, dev)
+        with torch.cuda.device(dev):
+            rc = lib.aa_sample_decode(model, images.data_ptr(), B, T, tau, stream_key(seed, "sample"), row0,
+                                      ids.data_ptr(), logp.data_ptr(), alpha.data_ptr(), beta.data_ptr(),
+                                      _lib.ptr(ws), ws.numel(), _lib.DECODE_FP32_ENCODER if self.fp32_encoder else 0,
+                                      _lib.stream_handle(), select_events)
+        _lib.check(rc, "sample_decode")
+        return ids, logp, alpha, beta
 
     def _aux_stream(self, dev) -> torch.cuda.Stream:
         """The side stream of ``aa_greedy_decode_aux`` on ``dev``: the process's "decode-aux" role

@@ -18,7 +18,7 @@ The class reuses ``adaptive_attention.Encoder2Decoder`` (encoder tail, packing, 
 ``fp32_encoder``, ``exact_vocab``); the packed weights carry NULL for the three absent parameters and
 every decode passes ``AA_DECODE_BASELINE``.  Only ``cf.base_lstm_hidden_size == 512`` decodes (the
 library returns its dims error otherwise).  Not built yet, each raising ``NotImplementedError`` before
-any GPU work: ``forward`` (training), ``beam_search``, multi-token ``decoder(...)``, ``device_parallel``,
+any GPU work: ``forward`` (training), ``beam_search``, ``sample``, multi-token ``decoder(...)``, ``device_parallel``,
 ``distributed_sampler`` / ``sharded_sampler``.
 """
 from __future__ import annotations
@@ -198,6 +198,9 @@ class Encoder2Decoder(_A.Encoder2Decoder):
 
     def beam_search(self, *args, **kwargs):
         raise _unsupported("beam_search")
+
+    def sample(self, *args, **kwargs):
+        raise _unsupported("sample")
 
     def sharded_sampler(self, *args, **kwargs):
         raise _unsupported("sharded_sampler")

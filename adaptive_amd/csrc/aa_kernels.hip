@@ -3427,4 +3427,6 @@ int aa_synth_uniform(float* dst, int64_t n, uint64_t key, int64_t start, double 
 #include "aa_train.hip"
 // beam-search decode (reuses k_lstm / k_atten / k_vocab and the encoder)
 #include "aa_beam.hip"
+// seeded temperature-sampling decode (the beam's step loop with one row per image)
+#include "aa_sample.hip"
 #endif

@@ -79,6 +79,26 @@ def uniform_f32(key: int, start: int, n: int, lo: float = 0.0, hi: float = 1.0) 
     return (lo + (hi - lo) * u).astype(np.float32)
 
 
+def gumbel_uniform(key: int, start: int, n: int) -> np.ndarray:
+    """u[i] = (2 * (splitmix64(key + (start+i+1)*GOLDEN) >> 41) + 1) / 2^24 as float64, i < n: the top
+    23 bits at the odd 24-bit grid points, so u is exact in fp32 and 2^-24 <= u <= 1 - 2^-24."""
+    with np.errstate(over="ignore"):
+        i = np.arange(start + 1, start + n + 1, dtype=np.uint64)
+        z = np.uint64(key) + i * np.uint64(GOLDEN)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(MIX1)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(MIX2)
+        z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(41)) * np.uint64(2) + np.uint64(1)).astype(np.float64) * INV24
+
+
+def gumbel_f32(key: int, start: int, n: int) -> np.ndarray:
+    """Standard Gumbel noise of the sampling decode (``Encoder2Decoder.sample``, ``aa_synth_gumbel``):
+    g[i] = fp32(-log(-log(u[i]))) for element counters start .. start+n-1, the logs in float64 and one
+    cast to fp32.  |g| < 17."""
+    u = gumbel_uniform(key, start, n)
+    return (-np.log(-np.log(u))).astype(np.float32)
+
+
 def symmetric_f32(key: int, n: int, bound: float) -> np.ndarray:
     """U(-bound, bound): fp32((2u - 1) * bound)."""
     return ((2.0 * uniform24(key, 0, n) - 1.0) * float(bound)).astype(np.float32)

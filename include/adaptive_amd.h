@@ -346,6 +346,39 @@ AA_API int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int3
                           float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
                           aa_stream_t stream, aa_event_t* vocab_events);
 
+/* ---- seeded temperature-sampling decode ---------------------------------------------------------
+ * Not in the reference: semantics defined here and in tests/sample_oracle.py SampleOracle.  One
+ * caption per image drawn from the model's own distribution by Gumbel-max over the exact fp32 logits
+ * (aa_beam_decode's default logits), the same decoder step as aa_greedy_decode, from <start> = 1; all
+ * T steps run (no <end> handling).  At step t, image b, with x[v] the logits (v < vocab):
+ *   y[v]  = x[v] / temperature                                    (fp32)
+ *   e     = ((row0 + b) * T + t) * vocab + v                      (64-bit element counter)
+ *   u     = (2 * (splitmix64(key + (e + 1) * GOLDEN) >> 41) + 1) * 2^-24    (exact, inside (0, 1))
+ *   g     = -log(-log(u))
+ *   token = argmax_v (y[v] + g), ties to the smaller v; it is the input of step t + 1
+ *   logp  = y[token] - (max y + log sum exp(y - max y))           (tempered log-probability)
+ * key: the stream key (adaptive_amd.synth.stream_key(seed, "sample")); GOLDEN = 0x9E3779B97F4A7C15,
+ * splitmix64 as in aa_synth_uniform.  The same (key, row0, T) gives the same output bit for bit, and
+ * an image's draw depends only on its global row row0 + b: a batch sharded by rows (each shard with its
+ * row0) samples what the whole batch would.
+ * Outputs: ids [B,T] int64 and logp [B,T] (required); alpha [B,T,P] and beta [B,T] may be NULL.
+ * Checks, in aa_beam_decode's order: model (NULL / dims / buffer / alignment), vocab <= 16384 (else
+ * AA_ERR_DIMS), then AA_ERR_SHAPE for B < 0, T < 0, a temperature that is not finite and > 0, row0 < 0
+ * or any flag other than AA_DECODE_FP32_ENCODER (AA_DECODE_BASELINE included: there are no no-sentinel
+ * kernels on this path); then B == 0 or T == 0 returns AA_OK before any pointer is looked at; then
+ * AA_ERR_SHAPE if (row0 + B) * T * vocab exceeds 2^62, NULL pointers, alignment, workspace size.
+ * select_events (may be NULL): 2T hipEvent handles, pair t handed to step t's selection launch
+ * (k_sample_select), for per-launch timing. */
+AA_API size_t aa_sample_workspace_bytes(const aa_dims* dims, int32_t B, int32_t T);
+AA_API int aa_sample_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, float temperature,
+                            uint64_t key, int64_t row0, int64_t* ids, float* logp, float* alpha,
+                            float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
+                            aa_stream_t stream, aa_event_t* select_events);
+
+/* The sampling decode's noise on its own (same values as adaptive_amd.synth.gumbel_f32 up to the
+ * rounding of two logf): dst[i] = g of element counter start + i, i < n, as defined above. */
+AA_API int aa_synth_gumbel(float* dst, int64_t n, uint64_t key, int64_t start, aa_stream_t stream);
+
 /* Full fp32 vocab logits scores[B,V] = u W_m^T + b_m (AdaptiveBlock.mlp, adaptive_attention.py:132)
  * for given u = c_hat + h rows [B,H] (fp32 MFMA GEMM). */
 AA_API int aa_vocab_logits(const aa_model* m, int32_t B, const float* u, float* scores,
