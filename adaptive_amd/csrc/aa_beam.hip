@@ -16,11 +16,15 @@
 // Kernels: the greedy path's k_lstm (gathering h / c from each row's parent) and k_atten (kdiv =
 // K rows per image), the exact fp32 vocab GEMM k_vocab writing the logits, then k_beam_select
 // (one workgroup per image: row max / log-sum-exp / top-K in registers, K x K merge) and
-// k_beam_final (backtrace).
+// k_beam_final (backtrace).  The step's kernels and the encoder are other units': they are reached
+// through the launch functions of aa_internal.hpp.  The two exact fp32 vocab GEMMs are this unit's:
+// k_vexact (sampling's too) and k_vocab, whose arithmetic it shares (the greedy path's exact-vocab
+// stage and aa_vocab_logits call vocab_launch).
+#include "aa_internal.hpp"
+
 namespace aa {
 
 constexpr int BEAM_MAX = 8;      // AA_MAX_BEAM
-constexpr int BEAM_VPT = 64;     // logits held per thread in k_beam_select: V <= 256 * 64
 
 // dst[r][:] = src[r / K][:]  (n a multiple of 4)
 __global__ void k_expand_rows(const float* __restrict__ src, int B, int K, int n, float* __restrict__ dst) {
@@ -166,6 +170,56 @@ __global__ __launch_bounds__(256) void k_gsumm(int R, int V, int Vp, const float
   const float2 sm = granule_summary(x, valid, li, lh);
   const int row = rb * 32 + sum_row(li, lh);
   if (!(li & 1) && row < R) gsum[(int64_t)row * NG + g] = sm;
+}
+
+// ---------------------------------------------------------------------------------------------
+// D3 (exact path): logits = u W_m^T + b_m (AdaptiveBlock.mlp, adaptive_attention.py:132) with the
+// argmax of sampler (:201) fused into the epilogue: per-row max over the tile's columns by 64-bit
+// keys (lane shuffles, then LDS across the two column waves), one atomicMax per row per workgroup.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_vocab(int B, int H, int V, int Vp, int ld, const float* __restrict__ u,
+                                               const float* __restrict__ W, const float* __restrict__ bias,
+                                               float* __restrict__ scores, uint64_t* __restrict__ keys) {
+  constexpr int BM = 64, BN = 64;
+  __shared__ __attribute__((aligned(16))) float lds[Tile<BM, BN>::LDS_FLOATS];
+  const int MT = (B + BM - 1) / BM, NTn = Vp / BN;
+  const int L = xcd_remap(blockIdx.x, MT * NTn);
+  const int nt = L / MT, mt = L % MT;
+  ARowMajor al{u, H, mt * BM, B};
+  WRowMajor wl{W, H, nt * BN};
+  floatx16 acc[NP_VOCAB][1][1];
+  gemm_mainloop_np<BM, BN, NP_VOCAB>(al, wl, H / BK, lds, acc);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
+  const int col = nt * BN + wn * 32 + (lane & 31);
+  const bool valid = col < V;
+  const float bv = bias[col];
+  uint64_t best[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float p01 = acc[0][0][0][r] + acc[1][0][0][r], p23 = acc[2][0][0][r] + acc[3][0][0][r];
+    const float p45 = acc[4][0][0][r] + acc[5][0][0][r], p67 = acc[6][0][0][r] + acc[7][0][0][r];
+    const float x = ((p01 + p23) + (p45 + p67)) + bv;
+    const int row = mt * BM + wm * 32 + acc_row(r, lane);
+    if (scores && valid && row < B) scores[(int64_t)row * ld + col] = x;
+    uint64_t k = valid ? argmax_key(x, col) : 0ull;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+      const uint64_t y = shfl_xor_u64(k, o);
+      k = y > k ? y : k;
+    }
+    best[r] = k;
+  }
+  uint64_t* red = reinterpret_cast<uint64_t*>(lds);  // [2 column waves][64 rows]
+  if ((lane & 31) == 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wn * 64 + wm * 32 + acc_row(r, lane)] = best[r];
+  }
+  __syncthreads();
+  if (t < 64) {
+    const uint64_t a = red[t], c = red[64 + t];
+    const int row = mt * BM + t;
+    if (row < B && keys) atomicMax(reinterpret_cast<unsigned long long*>(keys + row), (unsigned long long)(a > c ? a : c));
+  }
 }
 
 // k_vexact (the beam's default vocab stage): exact fp32 logits -- k_vocab's arithmetic (the same
@@ -555,9 +609,11 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
 }
 
 struct BeamWS {
-  float *a_g, *V, *vwv, *vg, *xg1, *xg, *h[2], *c[2], *s, *u, *part, *logits, *cum, *ahist, *bhist;
+  EncWS e;  // of the B images (+ xg1: their x_g, expanded to the rows' r.xg)
+  RowWS r;  // of the R = B K rows
+  float *xg1, *logits, *cum, *ahist, *bhist;
   float2* gsum;
-  bf16x8 *hsp[2], *u3;
+  bf16x8* u3;
   int64_t *tok0, *tok;
   int *par, *fin, *htok, *hpar, *path;
 };
@@ -565,20 +621,9 @@ static BeamWS carve_beam(char* base, const Layout& L, int B, int T, int K, size_
   Carver c{base};
   BeamWS w;
   const size_t R = (size_t)B * K;
-  w.a_g = c.take<float>((size_t)B * L.C);
-  w.V = c.take<float>((size_t)B * P * L.H);
-  w.vwv = c.take<float>((size_t)B * P * PP);
-  w.vg = c.take<float>((size_t)B * L.E);
+  w.e = carve_enc(c, L, B);
   w.xg1 = c.take<float>((size_t)B * L.N5);
-  w.xg = c.take<float>(R * L.N5);
-  for (int i = 0; i < 2; ++i) {
-    w.h[i] = c.take<float>(R * L.H);
-    w.c[i] = c.take<float>(R * L.H);
-    w.hsp[i] = c.take<bf16x8>(hsp_frags(L, (int)R));
-  }
-  w.s = c.take<float>(R * L.H);
-  w.u = c.take<float>(R * L.H);
-  w.part = c.take<float>(R * (L.H / 16) * PART);
+  w.r = carve_rows(c, L, R);
   w.u3 = c.take<bf16x8>(hsp_frags(L, (int)R));
   w.logits = c.take<float>(R * L.Vp);
   w.gsum = c.take<float2>(R * (L.Vp / 32));
@@ -594,6 +639,17 @@ static BeamWS carve_beam(char* base, const Layout& L, int B, int T, int K, size_
   w.path = c.take<int>((size_t)B * T);
   *bytes = c.off;
   return w;
+}
+
+void vocab_launch(const Layout& L, const MP& p, int R, const float* u, float* scores, int ld, uint64_t* keys,
+                  hipStream_t s, aa_event_t* ev, int ei) {
+  AA_TLAUNCH(ev, ei, k_vocab, dim3(((R + 63) / 64) * (L.Vp / 64)), dim3(256), 0, s, R, L.H, L.V, L.Vp, ld, u, p.mlp_w,
+             p.mlp_b, scores, keys);
+}
+void vexact_launch(const Layout& L, const MP& p, int R, const float* u, float* logits, float2* gsum, hipStream_t s,
+                   aa_event_t* ev, int ei) {
+  AA_TLAUNCH(ev, ei, k_vexact, dim3(((R + VX_BM - 1) / VX_BM) * (L.Vp / VX_BN)), dim3(256), 0, s, R, L.H, L.V, L.Vp, u,
+             p.mlp_w, p.mlp_b, logits, gsum);
 }
 
 static int beam_check(const aa_dims* d, int B, int T, int K) {
@@ -636,38 +692,39 @@ int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, 
   const int H = L.H, R = B * K;
   const bool exact = (flags & AA_BEAM_FAST) == 0;  // default: exact fp32 logits
   // encoder tail for the B images; h0 / c0 / x_g expanded to the R = B*K rows
-  rc = encoder_launch(L, p, feats, B, w.a_g, w.V, w.vg, w.h[1], w.c[1], w.vwv, w.xg1, nullptr, 0, s);
+  const EncWS& e = w.e;
+  const RowWS& r = w.r;
+  rc = encoder_launch(L, p, feats, B, e.a_g, e.V, e.vg, r.h[1], r.c[1], e.vwv, w.xg1, nullptr, 0, s);
   if (rc) return rc;
   auto expand = [&](const float* src, int n, float* dst) {
     hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)(((int64_t)R * (n / 4) + 255) / 256)), dim3(256), 0, s, src, B, K,
                        n, dst);
   };
-  expand(w.h[1], H, w.h[0]);
-  expand(w.c[1], H, w.c[0]);
-  expand(w.xg1, L.N5, w.xg);
-  hipLaunchKernelGGL(k_split_rows, dim3((unsigned)(((int64_t)R * (H / 8) + 255) / 256)), dim3(256), 0, s, w.h[0], R, H,
-                     w.hsp[0]);
-  hipLaunchKernelGGL(k_fill_tok, dim3((R + 255) / 256), dim3(256), 0, s, w.tok0, R, (int64_t)1);  // <start>
+  expand(r.h[1], H, r.h[0]);
+  expand(r.c[1], H, r.c[0]);
+  expand(w.xg1, L.N5, r.xg);
+  split_rows_launch(r.h[0], R, H, r.hsp[0], s);
+  fill_tok_launch(w.tok0, R, 1, s);  // <start>
   AA_TRY(hipMemsetAsync(w.cum, 0, sizeof(float) * R, s));
   AA_TRY(hipMemsetAsync(w.fin, 0, sizeof(int) * R, s));
-  const int MT = (R + 63) / 64;
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
-    lstm_atten_launch(L, p, R, t ? w.tok : w.tok0, 1, w.V, w.vwv, w.xg, w.hsp[cur], w.c[cur], w.h[nxt], w.hsp[nxt],
-                      w.c[nxt], w.s, w.part, w.u, nullptr, nullptr, w.ahist + (size_t)t * R * P, P,
-                      w.bhist + (size_t)t * R, 1, nullptr, t, s, t ? w.par : nullptr, K, exact ? nullptr : w.u3);
+    lstm_atten_launch(L, p,
+                      {.B = R, .tok = t ? w.tok : w.tok0, .V = e.V, .vwv = e.vwv, .xg = r.xg, .hsp_in = r.hsp[cur],
+                       .c_in = r.c[cur], .h_out = r.h[nxt], .hsp_out = r.hsp[nxt], .c_out = r.c[nxt], .s = r.s,
+                       .part = r.part, .u = r.u, .ub3 = exact ? nullptr : w.u3, .alpha = w.ahist + (size_t)t * R * P,
+                       .beta = w.bhist + (size_t)t * R, .par = t ? w.par : nullptr, .kdiv = K, .ei = 2 * t},
+                      s);
     if (exact) {
       if (flags & AA_DECODE_EXACT_VOCAB) rec(vocab_events, 2 * t, s);
       // exact fp32 logits (k_vocab's fma chains, pitch Vp) and their granule summaries: one fused
       // launch (k_vexact), or -- AA_DECODE_EXACT_VOCAB, the cross-check -- k_vocab then k_gsumm
       if (flags & AA_DECODE_EXACT_VOCAB) {
-        hipLaunchKernelGGL(k_vocab, dim3(MT * (L.Vp / 64)), dim3(256), 0, s, R, H, L.V, L.Vp, L.Vp, w.u, p.mlp_w,
-                           p.mlp_b, w.logits, (uint64_t*)nullptr);
+        vocab_launch(L, p, R, r.u, w.logits, L.Vp, nullptr, s);
         hipLaunchKernelGGL(k_gsumm, dim3((unsigned)((((R + 31) / 32) * (L.Vp / 32) + 3) / 4)), dim3(256), 0, s, R,
                            L.V, L.Vp, w.logits, w.gsum);
       } else {
-        AA_TLAUNCH(vocab_events, 2 * t, k_vexact, dim3(((R + VX_BM - 1) / VX_BM) * (L.Vp / VX_BN)), dim3(256), 0, s,
-                   R, H, L.V, L.Vp, (const float*)w.u, p.mlp_w, p.mlp_b, w.logits, w.gsum);
+        vexact_launch(L, p, R, r.u, w.logits, w.gsum, s, vocab_events, 2 * t);
       }
       if (flags & AA_DECODE_EXACT_VOCAB) rec(vocab_events, 2 * t + 1, s);
       hipLaunchKernelGGL(k_beam_select3, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t, end_id < 0 ? -1 : end_id,

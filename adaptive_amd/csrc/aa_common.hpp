@@ -1,5 +1,5 @@
-// aa_common.hpp — constants and small device/host helpers shared by the decode kernels
-// (aa_kernels.hip) and the teacher-forced training kernels (aa_train.hip).
+// aa_common.hpp — constants and small device/host helpers shared by every translation unit (the
+// optimizer kernels included; what only the model's units share is in aa_internal.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,9 +13,12 @@ namespace aa {
 
 // Phase timestamps for tools/ktrace (an instrumented build only: -DAA_TS_ENABLE): thread 0 of each
 // workgroup writes s_memrealtime (100 MHz) to aa_ts_buf[kernel][blockIdx.x][slot].  Empty in the
-// product build.
+// product build.  Objects are compiled without relocatable device code, so each has its own copy of
+// the pointer: a unit whose kernels use AA_TS defines a setter of its copy with ts_set_local, and
+// aa_ts_setup (aa_kernels.hip) calls them all (that unit's own and the four k_lstm objects').
 #ifdef AA_TS_ENABLE
-__device__ uint64_t* aa_ts_buf = nullptr;
+static __device__ __attribute__((unused)) uint64_t* aa_ts_buf = nullptr;
+static inline int ts_set_local(void* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(aa_ts_buf), &buf, sizeof(buf)); }
 __device__ __forceinline__ void aa_ts(int kid, int slot) {
   if (threadIdx.x == 0 && aa_ts_buf) {
     uint64_t* p = aa_ts_buf + ((size_t)kid * 2048 + blockIdx.x) * 16 + slot;

@@ -1,57 +1,27 @@
-// aa_kernels.hip — MI355X (gfx950) kernels and C-ABI for the adaptive-attention greedy decode
-// ("Knowing When to Look"; reference: code_src/models/adaptive_attention.py,
-// code_src/models/baseline_attention.py).  See DESIGN.md for the data layout and rooflines.
+// aa_kernels.hip — MI355X (gfx950) kernels of the decode step behind k_lstm, and the C-ABI of the
+// step and greedy decode ("Knowing When to Look"; reference: code_src/models/adaptive_attention.py,
+// code_src/models/baseline_attention.py).  See DESIGN.md for the data layout and rooflines; the pack
+// and encoder kernels are in aa_encoder.hip, k_lstm in aa_lstm.hpp / aa_lstm.hip.
 //
 // Kernels (all arithmetic that defines an output is fp32):
-//   pack time (once per weight set)
-//     k_pack_lstm     W_hh / emb-part / v_g-part of W_ih and W_x re-laid in gate-interleaved tiles
-//     k_gemm_bias     table[v] = embed[v] . [W_ih(emb part); W_x(emb part)]^T   (V x 5H)
-//     k_pack_mlp      bf16 copy and row norms of W_m for the vocab screen
-//   encoder tail (once per batch)
-//     k_avgpool       a_g = AvgPool2d(7)(A)                           baseline_attention.py:46-47
-//     k_enc_v         V = relu(A^T W_a^T + b_a)  [B*49, H]             :50-51
-//     k_enc_heads     v_g | h0 | c0 = act(a_g [W_b;W_h0;W_c0]^T + b)   :53-60
-//     k_gemm_bias     VWv = V W_v^T (step-invariant, hoisted)          adaptive_attention.py:34
-//     k_gemm_bias     xg = v_g . [W_ih(v_g part); W_x(v_g part)]^T + b_ih + b_hh (step-invariant)
 //   decode step t (x T)
-//     k_lstm          gates = table[tok] + xg + h W_hh^T; LSTM cell; sentinel s = sigm(.) tanh(c')
-//                     baseline_attention.py:151-172, adaptive_attention.py:79-83
-//     k_atten         W_g h, W_s s, 49+1 tanh scores, softmax, context, beta mix, u = c_hat + h
-//                     adaptive_attention.py:26-58, 132 (input of mlp)
-//     k_vscreen       bf16 MFMA logits with a rigorous error bound -> per-tile candidate summary
-//     k_vrescore      exact fp32 logits of the candidates (MFMA-order fma chain) + first-index argmax
+//     k_lstm          (aa_lstm.hpp) gates = table[tok] + xg + h W_hh^T; LSTM cell; sentinel; the
+//                     projection partials; from step 1 on, step t-1's rescoring in the same launch
+//     k_atten5        W_g h, W_s s (the partials summed), 49+1 tanh scores, softmax, context, beta mix,
+//                     u = c_hat + h     adaptive_attention.py:26-58, 132 (input of mlp)
+//                     (k_atten: H = 256 / 768; k_atten5b: an image's beams together)
+//     k_vscreen8      bf16 MFMA logits with a rigorous error bound -> per-granule candidate summary
+//                     (k_vscreen2 / k_vscreen: the cross-check and the other shapes)
+//     fused rescore   exact fp32 logits of the candidates (MFMA-order fma chain) + first-index argmax,
+//                     in the next step's k_lstm<.., RS>; the last step's in k_vrescore
 //                     adaptive_attention.py:132, 201
-//   exact-vocab path (scores output / verification): k_vocab (fp32 MFMA GEMM + fused argmax) + k_finalize
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include <stdlib.h>
-#include <vector>
-
-#include "aa_common.hpp"
+//   exact-vocab path (scores output / verification): k_vocab (aa_beam.hip, with the other exact vocab
+//                     GEMM k_vexact: fp32 MFMA GEMM + fused argmax) + k_finalize
+//   small: k_fill_tok, k_key_ids, k_split_rows, k_logits_at, k_synth_uniform
+#include "aa_internal.hpp"
+#include "aa_lstm.hpp"
 
 namespace aa {
-
-// Write-through stores (agent-scope relaxed atomic stores = `global_store_* sc1`): the line leaves
-// for memory at once instead of sitting dirty in this XCD's L2 until the kernel-end writeback, which
-// the next launch waits for (MI355X_MICROARCH.md, boundary: + dirty bytes / 6 TB/s).  k_lstm's
-// outputs take them (the attention-projection partials, h / c / s / split-h); on k_atten5's u /
-// bf16 u / norms, the screen's summaries and k_enc_v4's V they measured slower.
-template <class T>
-__device__ __forceinline__ void st_wt(T* p, const T& v) {
-  if constexpr (sizeof(T) == 4) {
-    __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    static_assert(sizeof(T) == 8, "4- or 8-byte stores");
-    __hip_atomic_store(reinterpret_cast<uint64_t*>(p), __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-constexpr uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;
 
 // Vocab-screen error bound.  For one logit, the fp32 path (k_vocab / k_vrescore) computes
 // L = fl(sum_k u_k w_k) + b and the screen computes A = fl(sum_k bf16(u_k) bf16(w_k)) + b (the
@@ -92,1282 +62,10 @@ __device__ __forceinline__ float screen_bound(float2 un, float4 g) {
   const float uw = un.x * g.x;
   return SC_BF * (un.y * g.x + un.x * g.z) + SC_ACC * uw + EPS_ABS * (uw + g.y);
 }
-constexpr int VS_TILE = 32;     // screen summary granule: one (lbmax, top-2 ub) per row per 32 columns
-constexpr int RS_CAP = 2048;    // candidate list capacity per row in k_vrescore (else full row)
-// Exact fp32 logits (k_vocab and the rescoring) are NP_VOCAB independent fma chains over contiguous
-// K ranges (in the MFMA k order), combined as ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)), then + bias.
-constexpr int NP_VOCAB = 8;
-
-// ---------------------------------------------------------------------------------------------
-// Packed weight layout (float offsets into aa_model.packed), 64-float aligned regions.
-// ---------------------------------------------------------------------------------------------
-struct Layout {
-  int E, H, V, C;
-  int NH, NHp;   // heads rows E + 2H, padded to 64
-  int Vp;        // vocab rows padded to 128
-  int N5;        // 5H: 4 gates (packed tile order) + sentinel
-  size_t enc_a_w, enc_a_b, enc_w3, whh3, heads_w, heads_b, wv, wg, ws, wh, whh, wemb, wvg, bias5, table, mlp_w, mlp_b, mlp_wb, mlp_wn, mlp_gs, wgs, mlp_w3, enc_w4, heads_w4, wvg4, wv4;
-  size_t total_floats;
-};
-
-static inline size_t al64(size_t x) { return (x + 63) & ~size_t(63); }
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-static Layout make_layout(const aa_dims& d) {
-  Layout L;
-  L.E = d.embed; L.H = d.hidden; L.V = d.vocab; L.C = d.channels;
-  L.NH = L.E + 2 * L.H; L.NHp = rup(L.NH, 64);
-  L.Vp = rup(L.V, 128);
-  L.N5 = 5 * L.H;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o = al64(o + n); return r; };
-  L.enc_a_w = take((size_t)L.H * L.C);
-  L.enc_a_b = take(L.H);
-  L.enc_w3 = take((size_t)3 * L.H * L.C / 2);  // bf16 [H/32][C/16][3][64][8]
-  L.heads_w = take((size_t)L.NHp * L.C);
-  L.heads_b = take(L.NHp);
-  L.wv = take((size_t)PP * L.H);
-  L.wg = take((size_t)P * L.H);
-  L.ws = take((size_t)P * L.H);
-  L.wh = take(PP);
-  L.whh = take((size_t)4 * L.H * L.H);
-  L.whh3 = take((size_t)3 * 4 * L.H * L.H / 2);  // bf16 fragments [4H/32][H/16][3][64][8]
-  L.wemb = take((size_t)L.N5 * L.E);
-  L.wvg = take((size_t)L.N5 * L.E);
-  L.bias5 = take(L.N5);
-  L.table = take((size_t)L.V * L.N5);
-  L.mlp_w = take((size_t)L.Vp * L.H);
-  L.mlp_b = take(L.Vp);
-  L.mlp_wb = take((size_t)L.Vp * L.H / 2);  // bf16
-  L.mlp_wn = take((size_t)2 * L.Vp);  // ||w_n|| then ||w_n - bf16(w_n)|| (inflated)
-  L.mlp_gs = take((size_t)4 * (L.Vp / VS_TILE));  // float4 per granule: (max ||w_n||, max |b_n|, max ||dw_n||, 0)
-  L.wgs = take((size_t)(L.H / 16) * 2 * P * 16);  // [tile][98][16]: W_g rows then W_s rows, 16 units of the tile
-  L.mlp_w3 = take((size_t)3 * L.Vp * L.H / 2);    // W_m as 3 bf16 planes, fragments [Vp/32][H/16][3][64][8] (beam)
-  L.enc_w4 = take((size_t)3 * L.H * L.C / 2);     // W_a as 3 bf16 planes, 16x16x32 fragments [H/16][C/32][3][64][8]
-  L.heads_w4 = take((size_t)3 * L.NHp * L.C / 2);  // heads as 3 bf16 planes, 16x16x32 fragments [NHp/16][C/32][3][64][8]
-  L.wvg4 = take((size_t)3 * L.N5 * L.E / 2);       // W_vg (x_g GEMM) likewise [N5/16][E/32][3][64][8]
-  L.wv4 = take((size_t)3 * PP * L.H / 2);          // W_v (VWv GEMM) likewise [PP/16][H/32][3][64][8]
-  L.total_floats = o;
-  return L;
-}
-
-struct MP {  // resolved device pointers of the packed weights
-  const bf16x8 *enc_w3, *whh3, *mlp_w3, *enc_w4, *heads_w4, *wvg4, *wv4;
-  const float *enc_a_w, *enc_a_b, *heads_w, *heads_b, *wv, *wg, *ws, *wh, *whh, *wemb, *wvg, *bias5, *table, *mlp_w,
-      *mlp_b, *mlp_wn, *wgs;
-  const float4* mlp_gs;
-  const uint16_t* mlp_wb;
-};
-
-static MP resolve(const aa_model* m, const Layout& L) {
-  const float* b = static_cast<const float*>(m->packed);
-  MP p;
-  p.enc_a_w = b + L.enc_a_w; p.enc_a_b = b + L.enc_a_b;
-  p.enc_w3 = reinterpret_cast<const bf16x8*>(b + L.enc_w3);
-  p.whh3 = reinterpret_cast<const bf16x8*>(b + L.whh3);
-  p.mlp_w3 = reinterpret_cast<const bf16x8*>(b + L.mlp_w3);
-  p.enc_w4 = reinterpret_cast<const bf16x8*>(b + L.enc_w4);
-  p.heads_w4 = reinterpret_cast<const bf16x8*>(b + L.heads_w4);
-  p.wvg4 = reinterpret_cast<const bf16x8*>(b + L.wvg4);
-  p.wv4 = reinterpret_cast<const bf16x8*>(b + L.wv4);
-  p.heads_w = b + L.heads_w; p.heads_b = b + L.heads_b;
-  p.wv = b + L.wv; p.wg = b + L.wg; p.ws = b + L.ws; p.wh = b + L.wh;
-  p.whh = b + L.whh; p.wemb = b + L.wemb; p.wvg = b + L.wvg; p.bias5 = b + L.bias5; p.table = b + L.table;
-  p.mlp_w = b + L.mlp_w; p.mlp_b = b + L.mlp_b;
-  p.mlp_wb = reinterpret_cast<const uint16_t*>(b + L.mlp_wb); p.mlp_wn = b + L.mlp_wn; p.wgs = b + L.wgs;
-  p.mlp_gs = reinterpret_cast<const float4*>(b + L.mlp_gs);
-  return p;
-}
-
-// ---------------------------------------------------------------------------------------------
-// small math helpers (accurate libm: expf/tanhf from the device library, no fast-math)
-// ---------------------------------------------------------------------------------------------
-
-// Argmax key: larger logit wins; on equal logits the smaller vocab index wins (torch max(2)[1]
-// returns the first maximal index, adaptive_attention.py:201).
-__device__ __forceinline__ uint64_t argmax_key(float x, int n) {
-  uint32_t u = __float_as_uint(x);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)n);
-}
-// order-preserving map of a (finite) float to u32: a < b  <=>  order_key(a) < order_key(b)
-__device__ __forceinline__ uint32_t order_key(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-__device__ __forceinline__ int64_t key_token(uint64_t k) { return (int64_t)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFu)); }
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o) {
-  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-  lo = __shfl_xor(lo, o, 64);
-  hi = __shfl_xor(hi, o, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t k) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t x = shfl_xor_u64(k, o);
-    k = x > k ? x : k;
-  }
-  return k;
-}
-
-// Element (row m, k) of a [rows][K] bf16 matrix stored in MFMA-fragment order (32-row blocks x
-// 16-wide k chunks x 64 lanes x 8): lane l of a fragment holds row (l & 31), k = 8 (l >> 5) + e.
-__device__ __forceinline__ int64_t frag_off(int m, int k, int K) {
-  return (((int64_t)(m >> 5) * (K >> 4) + (k >> 4)) * 64 + (m & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
-}
-
-// fp32 -> bf16, round to nearest even (finite inputs)
-__device__ __forceinline__ uint16_t f2bf(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// ---------------------------------------------------------------------------------------------
-// E0: a_g[b, c] = (sum_p A[b, c, p]) / 49, sequential fp32 sum in p order (the order of ATen's
-// cpu_avg_pool inner loop), one wave per 64 channels staged through LDS with 16-B loads.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_avgpool(const float* __restrict__ feats, int64_t nch, float* __restrict__ a_g) {
-  __shared__ float buf[4][64 * P];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t ch0 = ((int64_t)blockIdx.x * 4 + w) * 64;
-  const int nhere = ch0 < nch ? (int)(nch - ch0 < 64 ? nch - ch0 : 64) : 0;
-  const int nf4 = nhere * P / 4;  // nhere is a multiple of 32 -> whole float4s
-  const float4* src = reinterpret_cast<const float4*>(feats + ch0 * P);
-  float4* dst = reinterpret_cast<float4*>(buf[w]);
-  for (int q = lane; q < nf4; q += 64) dst[q] = src[q];
-  __syncthreads();
-  if (lane < nhere) {
-    const float* row = buf[w] + lane * P;
-    float s = 0.f;
-    for (int p = 0; p < P; ++p) s += row[p];
-    a_g[ch0 + lane] = s / 49.0f;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// E1: V = relu(A_rows W_a^T + b_a).  A row m = b*49 + p of the virtual [B*49, C] matrix is
-// column p of image b's [C, 49] NCHW block: read straight from the feature map (no transpose
-// pass), lanes over consecutive rows -> contiguous addresses.
-// ---------------------------------------------------------------------------------------------
-template <int BM>
-struct ANCHW {
-  // Per-thread row base pointer computed once (the thread's row is the same for every i and
-  // K-step: q % BM == t % BM); a K-step only adds k * 49.
-  const float* base;
-  __device__ __forceinline__ void init(const float* F, int C, int m0, int M) {
-    const int m = m0 + (int)(threadIdx.x % BM);
-    const int mc = m < M ? m : M - 1;  // clamp, never zero (see ARowMajor)
-    const int b = mc / P, p = mc - b * P;
-    base = F + (int64_t)b * C * P + p;
-  }
-  __device__ __forceinline__ void map(int q, int& r, int& kq) const { r = q % BM; kq = q / BM; }
-  __device__ __forceinline__ float4 load(int /*i*/, int q, int k0) const {
-    const float* s = base + (k0 + 4 * (q / BM)) * P;
-    return make_float4(s[0], s[P], s[2 * P], s[3 * P]);
-  }
-};
-
-__global__ __launch_bounds__(256) void k_enc_v(const float* __restrict__ feats, int B, int C, int H,
-                                               const float* __restrict__ W, const float* __restrict__ bias,
-                                               float* __restrict__ V) {
-  constexpr int BM = 64, BN = 64;
-  __shared__ __attribute__((aligned(16))) float lds[Tile<BM, BN>::LDS_FLOATS];
-  const int M = B * P, MT = (M + BM - 1) / BM, NTn = H / BN;
-  const int L = xcd_remap(blockIdx.x, MT * NTn);
-  const int mt = L / NTn, nt = L % NTn;  // n fastest: the A tile is shared inside an XCD
-  ANCHW<BM> al;
-  al.init(feats, C, mt * BM, M);
-  WRowMajor wl{W, C, nt * BN};
-  floatx16 acc[1][1];
-  gemm_mainloop<BM, BN>(al, wl, C / BK, lds, acc);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-  const int col = nt * BN + wn * 32 + (lane & 31);
-  const float bv = bias[col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = mt * BM + wm * 32 + acc_row(r, lane);
-    if (row < M) V[(int64_t)row * H + col] = reluf_(acc[0][0][r] + bv);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// E1 (default): the same V on bf16 MFMA with 3-way split operands ("bf16x3"), fp32-accurate.
-// Every fp32 operand x is split exactly as x = x0 + x1 + x2 + r with x_i bf16 (x0 = bf16(x),
-// x1 = bf16(x - x0), x2 = bf16(x - x0 - x1); each difference is exact in fp32, |r| <= 2^-24 |x|).
-// a.w is accumulated from the six partial products with i + j <= 2 (smallest first); the three
-// dropped ones are <= 2^-24 |a w| each, so the result is as accurate as an fp32 GEMM (whose own
-// accumulation error over K = 2048 dominates), at 6 bf16 MFMAs (6 x 32 cycles) per 32x32x16
-// block instead of 8 fp32 MFMAs (8 x 64 cycles).
-//   W: pre-split at pack time into MFMA-fragment order, enc_w3[nb][kc][q][lane][8] (1 KB per
-//      fragment: lane l holds W[32 nb + (l & 31)][16 kc + 8 (l >> 5) + j]) and read straight into
-//      VGPRs one stage ahead (each fragment is one coalesced 16-B-per-lane load).
-//   A: read from the NCHW feature map (row m = b*49 + p, column = channel; lanes over consecutive
-//      rows -> contiguous addresses), split in registers, staged in LDS as three bf16 planes
-//      [row][k] with an 80-B pitch (conflict-free ds_read_b128 / ds_write_b128).
-// Tile 128 x 128 per 256-thread workgroup; each wave owns 128 x 32 (4 blocks of 32 x 32: its own
-// W columns, the A rows shared through LDS);
-// K in stages of 32 (two k16 MFMA steps), A double-buffered in LDS, A and W prefetched a stage
-// ahead in registers.
-// ---------------------------------------------------------------------------------------------
-constexpr int EV_BM = 128, EV_BN = 128, EV_BK = 32, EV_LD = 40;  // LDS pitch in bf16 (80 B)
-
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  const float r2 = r1 - (float)m;
-  l = (__bf16)r2;
-}
-
-__global__ __launch_bounds__(256, 2) void k_enc_v3(const float* __restrict__ feats, int B, int C, int H,
-                                                   const bf16x8* __restrict__ W3, const float* __restrict__ bias,
-                                                   float* __restrict__ V) {
-  __shared__ __attribute__((aligned(16))) __bf16 As[2][3][EV_BM * EV_LD];
-  const int M = B * P, MT = (M + EV_BM - 1) / EV_BM, NTn = H / EV_BN, KC = C / 16;
-  const int L = xcd_remap(blockIdx.x, MT * NTn);
-  const int mt = L / NTn, nt = L % NTn;  // n fastest: the A tile is shared inside an XCD
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  // A staging: thread -> row r (0..127), k-half kh: k = 16 kh + i, i < 16, of each 32-stage
-  const int r = t & (EV_BM - 1), kh = t >> 7;
-  int m = mt * EV_BM + r;
-  m = m < M ? m : M - 1;  // clamp, never zero (rows >= M are not stored)
-  const int bi = m / P, pi = m - bi * P;
-  const float* arow = feats + (int64_t)bi * C * P + pi + (int64_t)(16 * kh) * P;
-  // W fragments of this wave: its own 32-column block (no fragment is loaded by two waves)
-  const int nb0 = (nt * EV_BN + wave * 32) / 32;
-  const bf16x8* wf0 = W3 + (size_t)nb0 * KC * 3 * 64 + lane;
-  float ra[16];
-  bf16x8 wa[2][3], wb[2][3];  // [sub][q], two stages in flight
-  floatx16 acc[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[a][i] = 0.f;
-
-  auto gload_a = [&](int s) {
-    const float* src = arow + (int64_t)(EV_BK * s) * P;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ra[i] = src[i * P];
-  };
-  auto gload_w = [&](int s, bf16x8 (&w)[2][3]) {
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) w[sub][q] = wf0[((size_t)(2 * s + sub) * 3 + q) * 64];
-  };
-  auto lstore_a = [&](int buf) {
-    bf16x8 h[2], md[2], lo[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      __bf16 x0, x1, x2;
-      split3(ra[i], x0, x1, x2);
-      h[i >> 3][i & 7] = x0;
-      md[i >> 3][i & 7] = x1;
-      lo[i >> 3][i & 7] = x2;
-    }
-    const int o = r * EV_LD + 16 * kh;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      *reinterpret_cast<bf16x8*>(&As[buf][0][o + 8 * j]) = h[j];
-      *reinterpret_cast<bf16x8*>(&As[buf][1][o + 8 * j]) = md[j];
-      *reinterpret_cast<bf16x8*>(&As[buf][2][o + 8 * j]) = lo[j];
-    }
-  };
-  auto compute = [&](int buf, const bf16x8 (&w)[2][3]) {
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        bf16x8 fa[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-          fa[q] = *reinterpret_cast<const bf16x8*>(&As[buf][q][(a * 32 + li) * EV_LD + 16 * sub + 8 * lh]);
-        floatx16 x = acc[a];
-        x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], w[sub][0], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], w[sub][1], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], w[sub][2], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], w[sub][0], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], w[sub][1], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], w[sub][0], x, 0, 0, 0);
-        acc[a] = x;
-      }
-    }
-  };
-
-  const int ns = C / EV_BK;  // even (C % 64 == 0 checked by the host)
-  gload_a(0);
-  gload_w(0, wa);
-  lstore_a(0);
-  gload_a(1);
-  gload_w(1, wb);
-  __syncthreads();
-  // No branches around the prefetch loads (a branch makes the compiler's vmcnt bookkeeping assume
-  // the worst at the join and drain the A prefetch inside the MFMA stream): past the end the
-  // stage index is clamped and the extra loads / LDS stores are harmless.
-  for (int s = 0; s < ns; s += 2) {
-    const int s2 = s + 2 < ns ? s + 2 : ns - 1, s3 = s + 3 < ns ? s + 3 : ns - 1;
-    // stage s: A in As[0], W in wa; A of s+1 in ra, W of s+1 in wb
-    // (sched_barrier: keep the scheduler from hoisting the split of a just-issued A prefetch into
-    //  the MFMA stream above it, which would wait for the load right away)
-    lstore_a(1);
-    gload_a(s2);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(0, wa);
-    gload_w(s2, wa);
-    __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-    // stage s+1: A in As[1], W in wb (As[0] is free: its last reader passed the barrier)
-    lstore_a(0);
-    gload_a(s3);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(1, wb);
-    gload_w(s3, wb);
-    __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  const int col = nt * EV_BN + wave * 32 + li;
-  const float bv = bias[col];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = mt * EV_BM + a * 32 + acc_row(i, lane);
-      if (row < M) V[(int64_t)row * H + col] = reluf_(acc[a][i] + bv);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// E1 (default at H = 128 NCB): the same bf16x3 V, one workgroup per TWO IMAGES and all H columns,
-// so the feature map is read from HBM exactly once and the grid is B/2 workgroups (256 at
-// B = 512: one per CU).  k_enc_v3's 128 x 128 tiles re-read every A row block once per column
-// tile (4x the A traffic through L2, 431 MB of HBM per launch against 260 MB algorithmic).
-//   rows: the 98 rows m = 98 wg .. 98 wg + 97 (images 2 wg, 2 wg + 1), computed as 7 blocks of
-//         16 rows of v_mfma_f32_16x16x32_bf16 (rows 98..111 of the tile are never stored);
-//   columns: wave w owns NCB 16-column blocks [16 NCB w, 16 NCB (w + 1)), all 7 row blocks
-//         (7 NCB accumulators of 4 floats);
-//   A: 16 dword loads per thread per 32-channel stage (lanes over consecutive rows: contiguous
-//      addresses), split in registers, three bf16 planes [row][k] in LDS with a 96-B pitch
-//      (conflict-free 16x16x32 ds_read_b128 fragment reads), double-buffered, one stage ahead;
-//   W: pre-split at pack time in 16x16x32 B-fragment order (enc_w4[nb][kc][q][lane][8], lane l
-//      holds W[16 nb + (l & 15)][32 kc + 8 (l >> 4) + j]); each column pair's fragments of stage
-//      s + 1 are loaded straight into VGPRs right after the pair's last MFMA of stage s.
-// The six products per block run smallest first, as in k_enc_v3 (fp32-accurate).
-// The avg-pool a_g (k_avgpool) is fused: the staging threads also put each stage's fp32 values in
-// LDS as [image][channel][p], and one wave per stage (rotating) sums every channel of both images
-// sequentially in p order and divides by 49 -- k_avgpool's arithmetic, bit-identical to ATen.
-// ---------------------------------------------------------------------------------------------
-// The feature map is read once per batch: non-temporal loads keep the 205 MB stream from
-// evicting the step kernels' working set (V, W_m, the token table) of the batches in flight.
-constexpr int E4_ROWS = 98, E4_RB = 7, E4_LD = 48;  // rows per workgroup, 16-row blocks, LDS pitch (bf16)
-constexpr int E4_SP = 52, E4_MAXC = 2048;           // a_g staging pitch (floats), largest channel count
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-// NW waves (8 or 16): each wave owns NCB 16-column blocks (H = 16 NCB NW); the A staging is done by
-// the first 512 threads either way.  NW = 16 (four waves per SIMD instead of two, half the columns
-// each; what H = 512 launches): k_enc_v4 247 -> 242 us, sequential decode +0.9 % (A/B, two rounds)
-constexpr int ENC4_NW = 16;
-
-template <int NCB, int NW = 8>
-__global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ feats, int B, int C,
-                                                const bf16x8* __restrict__ W4, const float* __restrict__ bias,
-                                                float* __restrict__ V, float* __restrict__ a_g) {
-  static_assert(NCB % 2 == 0, "columns are processed in pairs of 16-column blocks");
-  constexpr int H = 16 * NCB * NW, NPAIR = NCB / 2, PL = E4_RB * 16 * E4_LD;  // PL: one plane, bf16
-  constexpr int NT = 64 * NW;
-  const bool stager = NW == 8 || threadIdx.x < 512;
-  __shared__ __attribute__((aligned(16))) __bf16 As[2][3][PL];
-  __shared__ __attribute__((aligned(16))) float Sg[2][2 * 32 * E4_SP];  // fp32 stage copy for a_g
-  __shared__ __attribute__((aligned(16))) float Ag[2 * E4_MAXC];        // a_g of the two images
-  const int M = B * P, KC = C / 32;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int m0 = blockIdx.x * E4_ROWS;
-  // staging: thread t < 392 -> row r = t % 98, channels 8 kg .. 8 kg + 7 of each 32-channel stage;
-  // threads 392..511 fill garbage rows 98..105 (never stored) from a valid address.  (Each 8-lane
-  // group of the ds_write_b128 then hits 4 distinct 16-B slots: 2-way store conflicts.  Remapping the
-  // groups to 4 rows x 2 channel groups removes them but splits each wave's 256-B row-contiguous
-  // feature loads into 128-B pieces: measured 246 -> 256 us, not kept.)
-  const int sr = t < 4 * E4_ROWS ? t % E4_ROWS : E4_ROWS + (t & 7);
-  const int kg = t < 4 * E4_ROWS ? t / E4_ROWS : (t >> 3) & 3;
-  const bool stg = stager;
-  int m = m0 + (t < 4 * E4_ROWS ? sr : 0);
-  m = m < M ? m : M - 1;  // clamp, never zero (rows >= M are not stored)
-  const int bi = m / P, pi = m - bi * P;
-  const float* arow = feats + (int64_t)bi * C * P + pi + (int64_t)(8 * kg) * P;
-  const int so = sr * E4_LD + 8 * kg;
-  // fragment reads: lane l -> row 16 rb + (l & 15), k = 8 (l >> 4)
-  const int fo = (lane & 15) * E4_LD + 8 * (lane >> 4);
-  const bf16x8* wsrc = W4 + (size_t)(wave * NCB) * KC * 3 * 64 + lane;  // block nb = wave NCB + c
-  float ra[8];
-  bf16x8 wv[NCB][3];
-  floatx4 acc[E4_RB][NCB];
-#pragma unroll
-  for (int rb = 0; rb < E4_RB; ++rb)
-#pragma unroll
-    for (int c = 0; c < NCB; ++c) acc[rb][c] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  auto gload_a = [&](int s) {
-    const float* src = arow + (int64_t)(32 * s) * P;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ra[i] = __builtin_nontemporal_load(src + i * P);
-  };
-  auto gload_w = [&](int s, int c) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) wv[c][q] = wsrc[((size_t)c * KC * 3 + (size_t)s * 3 + q) * 64];
-  };
-  auto lstore_a = [&](int buf) {
-    bf16x8 x[3];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      __bf16 x0, x1, x2;
-      split3(ra[i], x0, x1, x2);
-      x[0][i] = x0; x[1][i] = x1; x[2][i] = x2;
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(&As[buf][q][so]) = x[q];
-    if (t < 4 * E4_ROWS) {  // sr = 49 image + p
-      const int img = sr >= P, pp = sr - img * P;
-      float* g = &Sg[buf][(img * 32 + 8 * kg) * E4_SP + pp];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g[i * E4_SP] = ra[i];
-    }
-  };
-
-  const int ns = KC;
-  if (stg) gload_a(0);
-#pragma unroll
-  for (int c = 0; c < NCB; ++c) gload_w(0, c);
-  if (stg) lstore_a(0);
-  if (stg) gload_a(ns > 1 ? 1 : 0);
-  __syncthreads();
-  for (int s = 0; s < ns; ++s) {
-    const int buf = s & 1, s1 = s + 1 < ns ? s + 1 : ns - 1, s2 = s + 2 < ns ? s + 2 : ns - 1;
-    // A of stage s+1 (in ra) into the other buffer: its last readers (stage s-1) passed the barrier
-    if (stg) {
-      lstore_a(buf ^ 1);
-      gload_a(s2);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const __bf16* Ab = &As[buf][0][fo];
-#pragma unroll
-    for (int cp = 0; cp < NPAIR; ++cp) {
-#pragma unroll
-      for (int rb = 0; rb < E4_RB; ++rb) {
-        bf16x8 fa[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) fa[q] = *reinterpret_cast<const bf16x8*>(Ab + q * PL + rb * 16 * E4_LD);
-        // the pair's two accumulator chains interleaved (each chain's product order unchanged:
-        // bit-identical), so no MFMA waits on its immediate predecessor
-        {
-          const int c0 = 2 * cp, c1 = c0 + 1;
-          floatx4 x = acc[rb][c0], y = acc[rb][c1];
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[c0][0], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[c1][0], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c0][1], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c1][1], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][2], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][2], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c0][0], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c1][0], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][1], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][1], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][0], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][0], y, 0, 0, 0);
-          acc[rb][c0] = x;
-          acc[rb][c1] = y;
-        }
-      }
-      gload_w(s1, 2 * cp);
-      gload_w(s1, 2 * cp + 1);
-      // re-read the A fragments for the next pair instead of keeping all 21 live (VGPR budget)
-      asm volatile("" ::: "memory");
-    }
-    // one wave per stage (rotating over waves 0..7) sums the stage's channels for a_g (giving the turns
-    // to waves 8..15, which do no A staging, measured 4 us slower at NW = 16)
-    if (wave == (s & 7)) {  // lane -> (image lane / 32, channel lane % 32)
-      const float* g = &Sg[buf][lane * E4_SP];
-      float sum = 0.f;
-#pragma unroll 4
-      for (int pp = 0; pp < 48; pp += 4) {  // 16-B reads (E4_SP * 4 B = 13 x 16 B), summed in p order
-        const float4 v = *reinterpret_cast<const float4*>(g + pp);
-        sum += v.x; sum += v.y; sum += v.z; sum += v.w;
-      }
-      sum += g[48];
-      Ag[(lane >> 5) * C + 32 * s + (lane & 31)] = sum / 49.0f;
-    }
-    __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // a_g of the workgroup's images (the last workgroup of an odd batch holds one)
-  for (int i = t; i < 2 * C; i += NT) {
-    const int img = 2 * blockIdx.x + (i >= C);
-    if (img < B) a_g[(int64_t)img * C + (i - (i >= C ? C : 0))] = Ag[i];
-  }
-  // epilogue: lane l holds column 16 nb + (l & 15), rows 16 rb + 4 (l >> 4) + i.  Stored straight
-  // from the accumulators, every store instruction wrote 64-B row pieces (16 columns x 4 rows): 1.39x
-  // the V bytes left L2 (r01 PMC).  Instead each 16-row block goes through LDS ([16][H + 4] floats,
-  // aliasing the A stages) and leaves as whole rows: the workgroup's 98 rows are one contiguous
-  // 98 H-float run of V, written by 16-B lanes, 1 KB per wave instruction.
-  float* Vs = reinterpret_cast<float*>(&As[0][0][0]);
-  constexpr int VSP = H + 4;  // pitch: rows 4 apart land 16 banks apart (conflict-free transposed writes)
-  static_assert(16 * VSP * 4 <= sizeof(As), "V staging must fit in the A stages");
-  float bvs[NCB];
-#pragma unroll
-  for (int c = 0; c < NCB; ++c) bvs[c] = bias[(wave * NCB + c) * 16 + (lane & 15)];
-#pragma unroll
-  for (int rb = 0; rb < E4_RB; ++rb) {
-    __syncthreads();  // the previous block's rows were read out (rb = 0: the A stages are free)
-#pragma unroll
-    for (int c = 0; c < NCB; ++c) {
-      const int col = (wave * NCB + c) * 16 + (lane & 15);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) Vs[(4 * (lane >> 4) + i) * VSP + col] = reluf_(acc[rb][c][i] + bvs[c]);
-    }
-    __syncthreads();
-    constexpr int F4 = 16 * H / 4;  // float4s of the block
-#pragma unroll
-    for (int q = t; q < F4; q += NT) {
-      const int r = q / (H / 4), c4 = q % (H / 4), tr = rb * 16 + r, row = m0 + tr;
-      if (tr < E4_ROWS && row < M)
-        *reinterpret_cast<float4*>(V + (int64_t)row * H + 4 * c4) = *reinterpret_cast<const float4*>(Vs + r * VSP + 4 * c4);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// E2: heads.  [v_g | h0 | c0] = a_g · [W_b; W_h0; W_c0]^T + b, relu / tanh / tanh by column.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_enc_heads(const float* __restrict__ a_g, int B, int C, int E, int H, int NHp,
-                                                   const float* __restrict__ W, const float* __restrict__ bias,
-                                                   float* __restrict__ v_g, float* __restrict__ h0, float* __restrict__ c0) {
-  constexpr int BM = 64, BN = 64;
-  __shared__ __attribute__((aligned(16))) float lds[Tile<BM, BN>::LDS_FLOATS];
-  const int MT = (B + BM - 1) / BM, NTn = NHp / BN;
-  const int L = xcd_remap(blockIdx.x, MT * NTn);
-  const int nt = L / MT, mt = L % MT;
-  ARowMajor al{a_g, C, mt * BM, B};
-  WRowMajor wl{W, C, nt * BN};
-  floatx16 acc[1][1];
-  gemm_mainloop<BM, BN>(al, wl, C / BK, lds, acc);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-  const int col = nt * BN + wn * 32 + (lane & 31);
-  if (col >= E + 2 * H) return;
-  const float bv = bias[col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = mt * BM + wm * 32 + acc_row(r, lane);
-    if (row >= B) continue;
-    const float x = acc[0][0][r] + bv;
-    if (col < E) v_g[(int64_t)row * E + col] = reluf_(x);
-    else if (col < E + H) h0[(int64_t)row * H + (col - E)] = tanhf(x);
-    else c0[(int64_t)row * H + (col - E - H)] = tanhf(x);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// E2 (default): the encoder's small GEMMs on bf16 MFMA with 3-way split operands (fp32-accurate, as
-// k_enc_v4): out[M x N] = A[M x K] W^T (+ bias), A fp32 row-major (lda K), W pre-split in 16x16x32
-// B-fragment order (k_pack_w4).  A workgroup owns 32 rows x 16 NB columns; its NWV waves each run
-// 1/NWV of K over the whole tile (v_mfma_f32_16x16x32_bf16, a fragments split in registers), and the
-// NWV partial tiles are summed in LDS as a fixed pairwise tree before bias and epilogue.  These GEMMs
-// are short (K = 256..2048, 32-row tiles): their time is the K loop's load latency, so K is spread
-// over waves (k_enc_heads' 64 x 64 fp32-MFMA tiles ran all K = 2048 per workgroup: ≈66 µs).
-//   MODE_HEADS: columns [0, E) -> v_g = relu, [E, E+H) -> h0 = tanh, [E+H, E+2H) -> c0 = tanh
-//   MODE_PLAIN: out0[row * ldo + col] = acc + (bias ? bias[col] : 0), col < N  (x_g, VWv)
-// ---------------------------------------------------------------------------------------------
-enum { MODE_HEADS = 0, MODE_PLAIN = 1 };
-template <int NB, int NWV, int MODE>
-__global__ __launch_bounds__(64 * NWV) void k_gemm3(const float* __restrict__ A, int M, int K, int N,
-                                                    const bf16x8* __restrict__ W4, const float* __restrict__ bias,
-                                                    float* __restrict__ out0, int ldo, float* __restrict__ h0,
-                                                    float* __restrict__ c0, int E, int H,
-                                                    bf16x8* __restrict__ hsp = nullptr, int64_t* __restrict__ tok0 = nullptr,
-                                                    int tok_n = 0, uint64_t* __restrict__ keys = nullptr, int key_n = 0) {
-  constexpr int BN = 16 * NB, TP = BN + 4;  // tile columns, LDS row pitch of a partial tile (floats)
-  if (MODE == MODE_HEADS && tok0) {  // k_decode_init's work (one-stream decode): <start> ids, cleared keys
-    const int i0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-    for (int i = i0; i < tok_n; i += stride) tok0[i] = 1;
-    for (int i = i0; i < key_n; i += stride) __hip_atomic_store(keys + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __shared__ __attribute__((aligned(16))) float Pt[NWV][32 * TP];
-  const int KC = K / 32, NTn = (N + BN - 1) / BN;
-  const int mt = blockIdx.x / NTn, nt = blockIdx.x % NTn;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int m0 = mt * 32;
-  const float* arow[2];
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb) {
-    int m = m0 + 16 * rb + (lane & 15);
-    m = m < M ? m : M - 1;  // clamp, never zero (rows >= M are not stored)
-    arow[rb] = A + (int64_t)m * K + 8 * (lane >> 4);
-  }
-  const bf16x8* wsrc = W4 + (size_t)(nt * NB) * KC * 3 * 64 + lane;
-  floatx4 acc[2][NB];
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int c = 0; c < NB; ++c) acc[rb][c] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int per = KC / NWV, kc0 = wave * per;  // K % (64 NWV) == 0 (checked by the host): per is even
-  float4 av[2][2][2];   // [slot][row block][half]
-  bf16x8 wv[2][NB][3];  // [slot][column block][plane]
-  auto load = [&](int slot, int kc) {
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-      av[slot][rb][0] = *reinterpret_cast<const float4*>(arow[rb] + 32 * kc);
-      av[slot][rb][1] = *reinterpret_cast<const float4*>(arow[rb] + 32 * kc + 4);
-    }
-#pragma unroll
-    for (int c = 0; c < NB; ++c)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) wv[slot][c][q] = wsrc[((size_t)c * KC * 3 + (size_t)kc * 3 + q) * 64];
-  };
-  auto step = [&](int slot) {
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-      bf16x8 fa[3];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __bf16 x0, x1, x2;
-        split3(f4c(av[slot][rb][i >> 2], i & 3), x0, x1, x2);
-        fa[0][i] = x0; fa[1][i] = x1; fa[2][i] = x2;
-      }
-#pragma unroll
-      for (int c = 0; c < NB; ++c) {
-        floatx4 x = acc[rb][c];
-        x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[slot][c][0], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[slot][c][1], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[slot][c][2], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[slot][c][0], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[slot][c][1], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[slot][c][0], x, 0, 0, 0);
-        acc[rb][c] = x;
-      }
-    }
-  };
-  // two chunks in flight; `per` is even; past the end the chunk index is clamped (harmless reloads)
-  const int last = kc0 + per - 1;
-  load(0, kc0);
-  load(1, kc0 + 1 < last ? kc0 + 1 : last);
-  for (int kc = kc0; kc < kc0 + per; kc += 2) {
-    step(0);
-    load(0, kc + 2 < last ? kc + 2 : last);
-    step(1);
-    load(1, kc + 3 < last ? kc + 3 : last);
-  }
-  // partial tile of this wave -> LDS [row][col]: lane holds column 16 c + (l & 15), rows 16 rb + 4 (l >> 4) + i
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int c = 0; c < NB; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) Pt[wave][(16 * rb + 4 * (lane >> 4) + i) * TP + 16 * c + (lane & 15)] = acc[rb][c][i];
-  __syncthreads();
-  for (int e = t; e < 32 * BN; e += 64 * NWV) {
-    const int r = e / BN, cl = e - r * BN, row = m0 + r, col = nt * BN + cl;
-    if (row >= M || col >= N) continue;
-    const int o = r * TP + cl;
-    float ps[NWV];
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) ps[w] = Pt[w][o];
-#pragma unroll
-    for (int st = 1; st < NWV; st *= 2)  // ((p0 + p1) + (p2 + p3)) + ...
-#pragma unroll
-      for (int w = 0; w + st < NWV; w += 2 * st) ps[w] += ps[w + st];
-    if (MODE == MODE_PLAIN) {
-      out0[(int64_t)row * ldo + col] = bias ? ps[0] + bias[col] : ps[0];
-    } else {
-      const float x = ps[0] + bias[col];
-      if (col < E) out0[(int64_t)row * E + col] = reluf_(x);
-      else if (col < E + H) {
-        const float hv = tanhf(x);
-        const int k = col - E;
-        h0[(int64_t)row * H + k] = hv;
-        if (hsp) {  // k_split_rows's fragments of h0 (the first step's GEMM operand), element by element
-          __bf16 x0, x1, x2;
-          split3(hv, x0, x1, x2);
-          __bf16* o = reinterpret_cast<__bf16*>(hsp + ((size_t)((row >> 5) * (H / 16) + (k >> 4)) * 3) * 64 +
-                                                (row & 31) + 32 * ((k >> 3) & 1)) + (k & 7);
-          o[0] = x0;
-          o[64 * 8] = x1;
-          o[128 * 8] = x2;
-        }
-      } else {
-        c0[(int64_t)row * H + (col - E - H)] = tanhf(x);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Generic C[M, N] = A[M, K] · W[N, K]^T (+ bias[N]) with a row-major store (ldc), N % 64 == 0.
-// Used for VWv (encoder), xg (encoder) and the per-token table (pack time).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gemm_bias(const float* __restrict__ A, int lda, int M, const float* __restrict__ W,
-                                                   int ldw, int N, int K, const float* __restrict__ bias,
-                                                   float* __restrict__ Cm, int64_t ldc) {
-  constexpr int BM = 64, BN = 64;
-  __shared__ __attribute__((aligned(16))) float lds[Tile<BM, BN>::LDS_FLOATS];
-  const int MT = (M + BM - 1) / BM, NTn = N / BN;
-  const int L = xcd_remap(blockIdx.x, MT * NTn);
-  const int nt = L / MT, mt = L % MT;
-  ARowMajor al{A, lda, mt * BM, M};
-  WRowMajor wl{W, ldw, nt * BN};
-  floatx16 acc[1][1];
-  gemm_mainloop<BM, BN>(al, wl, K / BK, lds, acc);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-  const int col = nt * BN + wn * 32 + (lane & 31);
-  const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = mt * BM + wm * 32 + acc_row(r, lane);
-    if (row < M) Cm[(int64_t)row * ldc + col] = bias ? acc[0][0][r] + bv : acc[0][0][r];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// D1: LSTM step + sentinel.  x_t = [embed[tok]; v_g] enters through two step-invariant terms:
-//   table[tok] = embed[tok] . W_ih[:, :E]^T (pack time)   and   xg[b] = v_g[b] . W_ih[:, E:]^T + b_ih + b_hh
-// (per batch), so the step's GEMM is only h_{t-1} W_hh^T (K = H).  Columns are packed per tile of
-// 16 hidden units as (i, f, g, o) x 16; the epilogue exchanges the tile through LDS so one thread
-// sees all four gates of a unit:
-//   c' = s(f) c + s(i) tanh(g),  h' = s(o) tanh(c')            (torch LSTM cell, gate order i,f,g,o)
-//   s  = sigmoid(x W_x^T + W_h . 0) * tanh(c')                  (Sentinel, h_{t-1} = 0 while sampling,
-//                                                                adaptive_attention.py:116-122)
-// with x W_x^T = table[tok][4H + j] + xg[b][4H + j].
-// The tile then contributes its 16 units to the attention projections W_g h' and W_s s
-// (Atten.affine_g / affine_s, adaptive_attention.py:35,45): part[b][tile][j] = sum_{u in tile}
-// (j < 49 ? h'_u W_g[j][u] : s_u W_s[j-49][u]); k_atten adds the H/16 partials in tile order.
-// ---------------------------------------------------------------------------------------------
-constexpr int PART = 128;  // partial-projection row pitch (W_g h outputs at 0..48, W_s s at 64..112)
-// Column of projection output j (0..97: W_g then W_s) in a partial row.  Each half
-// starts on a 256-B boundary, so every store instruction of the tile's projection phase (a 32 x 32
-// accumulator block: two rows x 32 columns) writes two whole 128-B lines (the write-through stores of
-// partial lines otherwise cost the memory side a read-modify-write each).
-__device__ __forceinline__ int part_col(int j) { return j < P ? j : 64 + (j - P); }
-
-// The GEMM h_{t-1} W_hh^T runs on bf16 MFMA with 3-way split operands (see k_enc_v3): h arrives
-// already split (hsp_in, written by the previous step's epilogue or k_split_rows) and W_hh is
-// pre-split at pack time, both in MFMA-fragment order, so every operand is one coalesced 16-B
-// load per lane straight into VGPRs -- no LDS staging.  Fragment index of (row block rb, k16
-// chunk kc, plane q): ((rb * KC + kc) * 3 + q) * 64 + lane.
-// 512 threads = 8 waves; wave w computes the whole 64x64 tile (2 x 2 blocks of 32x32) over K
-// chunks [w KC/8, (w+1) KC/8), so no fragment is loaded twice in the workgroup; the eight partial
-// tiles meet in LDS and are summed in a fixed tree ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)).
-__device__ __forceinline__ void x3_step(floatx16& acc, const bf16x8 (&a)[3], const bf16x8 (&w)[3]) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], w[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], w[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], w[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], w[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], w[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], w[0], acc, 0, 0, 0);
-}
-
-// Two-accumulator form (the lean k_lstm / k_lstm_gemm GEMMs): the three small products (i + j = 2)
-// go to one chain and the three large ones (i + j <= 1) to another, summed once at the end -- two
-// independent MFMA chains per wave instead of one dependent chain of 6 per chunk (sequential decode
-// +3 % in A/B; at least as accurate: the small terms no longer meet the large running sum chunk by
-// chunk).
-__device__ __forceinline__ void x3_step2(floatx16& sm, floatx16& bg, const bf16x8 (&a)[3], const bf16x8 (&w)[3]) {
-  sm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], w[0], sm, 0, 0, 0);
-  bg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], w[0], bg, 0, 0, 0);
-  sm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], w[1], sm, 0, 0, 0);
-  bg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], w[1], bg, 0, 0, 0);
-  sm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], w[2], sm, 0, 0, 0);
-  bg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], w[0], bg, 0, 0, 0);
-}
-
-constexpr int LS_CP = 68;  // k_lstm LDS tile pitch (floats): conflict-free cell reads
-
-// Cell epilogue shared by k_lstm (GEMM + cell in one launch) and k_lstm_cell (cell of a GEMM done
-// by k_lstm_gemm): thread -> row rr (0..63) of the tile, units u0, u0 + 1 of tile nt.
-// gate[g][q] = (h W_hh^T)[gate g, unit u0 + q] + (table[tok] + xg) -- the pre-activations;
-// sa + sb = x W_x^T of the sentinel; cprev = c_{t-1}; wsv = this thread's float4 of the tile's
-// W_g / W_s slice.  Writes c', h', s, the next step's split-h fragments, and the tile's partial
-// attention projections part[row][nt][j] = sum_{u in tile} (j < 49 ? h'_u W_g[j][u] : s_u W_s[j-49][u])
-// (v_mfma_f32_32x32x2f32, units (i, 8 + i) per instruction, i = 0..7 in order).
-constexpr int LS_HP = 68;    // pitch of the transposed h' / s tiles [unit][row]: conflict-free MFMA A reads
-constexpr int LS_WSP = 100;  // 98 projection outputs padded to whole float4s
-constexpr int LS_TAIL_FLOATS = 2 * 16 * LS_HP + 16 * LS_WSP;
-// SENT = false (the baseline spatial-attention model, baseline_attention.py:78-128: no sentinel): no
-// s (sa / sb are not read, the Ss tile and the s_out store are gone) and only the W_g half of the
-// projections -- waves 0..3 (cb < 2), columns 0..63 of a part row; c', h', the split-h fragments and
-// the W_g partials by the same arithmetic in the same order as with the sentinel.
-template <int H, bool SENT = true>
-__device__ __forceinline__ void lstm_cell_tail(int B, int m0, int nt, const float (&gate)[4][2], float2 sa, float2 sb,
-                                               float2 cprev, float4 wsv, float* Hs, float* h_out,
-                                               bf16x8* __restrict__ hsp_out, float* __restrict__ c_out,
-                                               float* __restrict__ s_out, float* __restrict__ part) {
-  constexpr int HP = LS_HP, WSP = LS_WSP, NTn = H / 16, KC = H / 16;
-  float* Ss = Hs + 16 * HP;   // [16][HP] s of the tile, transposed
-  float* Wsl = Ss + 16 * HP;  // [16][WSP] W_g / W_s rows (j < 49: W_g, else W_s) per unit
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int rr = t >> 3, u0 = (t & 7) * 2, m = m0 + rr, j = nt * 16 + u0;
-  {  // transpose the W_g / W_s slice to [unit][j] (j = 98, 99 are zero)
-    const int jj = t >> 2, uq = (t & 3) * 4;
-    if (t < (SENT ? 2 : 1) * P * 4) {
-      Wsl[(uq + 0) * WSP + jj] = wsv.x; Wsl[(uq + 1) * WSP + jj] = wsv.y;
-      Wsl[(uq + 2) * WSP + jj] = wsv.z; Wsl[(uq + 3) * WSP + jj] = wsv.w;
-    } else if (SENT && t < 2 * P * 4 + 32) {
-      const int z = t - 2 * P * 4;  // 32 zeros: j = 98, 99 for 16 units
-      Wsl[(z >> 1) * WSP + 2 * P + (z & 1)] = 0.f;
-    }
-  }
-  {
-    float hn[2], cn[2], sn[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const float i_ = sigmoidf_(gate[0][q]), f_ = sigmoidf_(gate[1][q]), g_ = tanhf(gate[2][q]),
-                  o_ = sigmoidf_(gate[3][q]);
-      cn[q] = f_ * (&cprev.x)[q] + i_ * g_;
-      const float tc = tanhf(cn[q]);
-      hn[q] = o_ * tc;
-      if constexpr (SENT) sn[q] = sigmoidf_((&sa.x)[q] + (&sb.x)[q]) * tc;
-    }
-    Hs[u0 * HP + rr] = hn[0];
-    Hs[(u0 + 1) * HP + rr] = hn[1];
-    if constexpr (SENT) {
-      Ss[u0 * HP + rr] = sn[0];
-      Ss[(u0 + 1) * HP + rr] = sn[1];
-    }
-    if (m < B) {
-      st_wt(reinterpret_cast<float2*>(c_out + (int64_t)m * H + j), make_float2(cn[0], cn[1]));
-      st_wt(reinterpret_cast<float2*>(h_out + (int64_t)m * H + j), make_float2(hn[0], hn[1]));
-      if constexpr (SENT) st_wt(reinterpret_cast<float2*>(s_out + (int64_t)m * H + j), make_float2(sn[0], sn[1]));
-      if (hsp_out) {
-        // next step's A fragments: k = j.. in chunk nt, lane (m % 32) + 32 * (u0 / 8), elements u0 % 8..
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        bf16x2 p0, p1, p2;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          __bf16 x0, x1, x2;
-          split3(hn[q], x0, x1, x2);
-          p0[q] = x0; p1[q] = x1; p2[q] = x2;
-        }
-        bf16x8* o = hsp_out + ((size_t)((m >> 5) * KC + nt) * 3) * 64 + (m & 31) + 32 * (u0 >> 3);
-        const int e = u0 & 7;
-        st_wt(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o) + e), p0);
-        st_wt(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o + 64) + e), p1);
-        st_wt(reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(o + 128) + e), p2);
-      }
-    }
-  }
-  AA_TS(0, 3);
-  __syncthreads();
-  // Wave -> one 32x32 block: rows rb*32.., columns cb = 0, 1: W_g j = 0..63; cb = 2, 3: W_s j = 0..63.
-  if (SENT || wave < 4) {
-    const int rb = wave & 1, cb = wave >> 1, li = lane & 31, lh = lane >> 5;
-    const float* X = cb < 2 ? Hs : Ss;
-    const int jj = (cb & 1) * 32 + li, jg = (cb < 2 ? 0 : P) + jj, jgc = jg < WSP ? jg : WSP - 1;
-    floatx16 pacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) pacc[r] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int u = i + 8 * lh;
-      const float av = X[u * HP + rb * 32 + li];
-      const float wv = jj < P ? Wsl[u * WSP + jgc] : 0.f;
-      pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wv, pacc, 0, 0, 0);
-    }
-    // (all 32 lanes store -- columns jj >= P hold zeros, their W values being 0 -- so the lines are whole)
-    const int col = (cb < 2 ? 0 : 64) + jj;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int mr = m0 + rb * 32 + acc_row(r, lane);
-      if (mr < B) st_wt(&part[((int64_t)mr * NTn + nt) * PART + col], pacc[r]);
-    }
-  }
-}
-
-// LDS-staged variant of the lean GEMM (the default): the same waves, blocks, K halves, chunk order
-// and MFMA sequence (bit-identical accumulators), but every fragment reaches LDS ONCE per workgroup by
-// LDS-DMA (global_load_lds, 1 KB per wave instruction) and the two waves that share it read it
-// from there.  The register-staged lean GEMM loads each fragment twice (768 KB per workgroup where
-// 384 KB are unique): its fragment stream was the GEMM phase's bound (tools/ktrace: loads alone 5.0
-// of the 8.9 us).  A stage = chunk `it` of both K halves = 24 fragments (24 KB): fragment f = 12 kh
-// + j, j < 6: A row block j / 3, plane j % 3; j >= 6: W column block (j - 6) / 3, plane (j - 6) % 3.
-// Wave w issues fragments 3w .. 3w + 2 of every stage.  Three stages in a ring: stage it + 2 is in
-// flight while stage it is multiplied (counted vmcnt, raw s_barrier: a __syncthreads() would drain
-// the DMAs).  `pre` runs after the first three stages are issued: it may issue exactly LS_GATHERS
-// ordinary loads (the cell's gathers), which the counted waits of the first two iterations account
-// for.  Ends with the K halves summed into Pt [column][row] (Pt aliases the ring).
-constexpr int LS_NB = 3;                      // ring stages (LS_NB - 1 in flight ahead of the one multiplied)
-constexpr int LS_STAGE = 24 * 64;             // bf16x8 per stage
-constexpr int LS_GATHERS = 12;                // ordinary loads issued by k_lstm's gathers (ISA-checked)
-constexpr int LS_NPW = 3;                     // fragments each wave DMAs per ring stage
-
-// s_waitcnt vmcnt(n) for an n that is a compile-time constant once the caller's loop is unrolled
-template <int V>
-__device__ __forceinline__ void vm_wait_c() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(V) : "memory"); }
-template <int V = 0>
-__device__ __forceinline__ void vm_wait(int n) {
-  if constexpr (V < 63) {
-    if (n == V) vm_wait_c<V>();
-    else vm_wait<V + 1>(n);
-  } else {
-    vm_wait_c<63>();
-  }
-}
-
-// Two more hooks for the fused-rescoring launch (k_lstm<.., RS>), both inside the ring at fixed
-// iterations so every wait stays a compile-time count: at iteration JK (after that iteration's
-// stage issue) `kdma` lets wave 0 issue ONE more LDS-DMA (the tile's published keys); at iteration JG
-// >= JK + NB (by then that DMA has landed: it is older than the stage the iteration waits for)
-// `mid` may read it from LDS and issue exactly NG2 ordinary loads per wave (the token-dependent
-// table gathers), which land under the remaining iterations.  JK < 0: no hooks.
-struct NoHook {
-  __device__ void operator()() const {}
-};
-template <int H, int NG = LS_GATHERS, int JK = -1, int JG = -1, int NG2 = 0, class F, class FK = NoHook,
-          class FM = NoHook>
-__device__ __forceinline__ void lstm_gemm_lds(const bf16x8* af0, const bf16x8* af1, const bf16x8* wf0,
-                                              const bf16x8* wf1, bf16x8* stg, float* Pt, F&& pre,
-                                              FK&& kdma = FK{}, FM&& mid = FM{}) {
-  constexpr int KC = H / 16, CP = LS_CP, N = KC / 2, NB = LS_NB < N ? LS_NB : N;
-  constexpr int LS_GATHERS = NG;  // ordinary loads `pre` issues (0: none)
-  static_assert(NB >= 3, "the ring needs at least three stages");
-  static_assert(JK < 0 || (JK + NB < N - 1 && JG >= JK + NB && JG < N - 1), "hook iterations");
-  // last stage issued before each hook's loads (they are younger than it, older than the next)
-  constexpr int SK = JK + NB < N - 1 ? JK + NB : N - 1, SG = JG + NB < N - 1 ? JG + NB : N - 1;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int a = (wave >> 1) & 1, c = wave & 1, kh = wave >> 2;
-  const bf16x8* src[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int f = 3 * wave + i, hf = f / 12, j = f % 12;
-    const bf16x8* base = j < 6 ? (j < 3 ? af0 : af1) : (j < 9 ? wf0 : wf1);
-    src[i] = base + (size_t)(hf * N * 3 + (j % 3)) * 64;  // + it * 3 * 64 per stage
-  }
-  auto issue = [&](int it) {
-    bf16x8* dst = stg + (it % NB) * LS_STAGE + (3 * wave) * 64;
-#pragma unroll
-    for (int i = 0; i < LS_NPW; ++i)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src[i] + (size_t)it * 3 * 64),
-                                       (__attribute__((address_space(3))) void*)(dst + i * 64), 16, 0, 0);
-  };
-  bf16x8 fa[2][3], fw[2][3];
-  auto lread = [&](int it, int set) {
-    const bf16x8* sb = stg + (it % NB) * LS_STAGE + kh * 12 * 64 + lane;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      fa[set][q] = sb[(3 * a + q) * 64];
-      fw[set][q] = sb[(6 + 3 * c + q) * 64];
-    }
-  };
-  floatx16 acc, acc2;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.f;
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int it = 0; it < NB; ++it) issue(it);
-  __builtin_amdgcn_sched_barrier(0);
-  pre();  // waits for its own older loads with vmcnt(3 NB); issues exactly LS_GATHERS loads
-  __builtin_amdgcn_sched_barrier(0);
-  // stage 0 landed (younger: stages 1 .. NB-1 and the gathers)
-  vm_wait(LS_NPW * (NB - 1) + LS_GATHERS);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  lread(0, 0);
-#pragma unroll
-  for (int it = 0; it < N; ++it) {
-    const int set = it & 1;
-    if (it + 1 < N) {
-      // stage it + 1 landed: younger are the stages issued after it (up to it + NB - 1) and, while
-      // it + 1 <= NB - 1, the gathers (issued after stage NB - 1)
-      const int last = it + NB - 1 < N - 1 ? it + NB - 1 : N - 1;
-      int younger = LS_NPW * (last - (it + 1)) + (it + 1 <= NB - 1 ? LS_GATHERS : 0);
-      if (JK >= 0 && it >= JG + 1 && it + 1 <= SG) younger += NG2;
-      if (JK >= 0 && it >= JK + 1 && it + 1 <= SK && wave == 0) younger += 1;
-      vm_wait(younger);
-      // every wave's stage-it reads retired (lgkmcnt) before any wave refills that buffer
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (it + NB < N) issue(it + NB);
-      if constexpr (JK >= 0) {
-        if (it == JK) {
-          __builtin_amdgcn_sched_barrier(0);
-          kdma();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (it == JG) {
-          __builtin_amdgcn_sched_barrier(0);
-          mid();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      lread(it + 1, set ^ 1);
-    }
-    x3_step2(acc2, acc, fa[set], fw[set]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] += acc2[r];  // large-product chain + small-product chain
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // ring free: Pt aliases it
-  const int li = lane & 31, lh = lane >> 5;
-  float* dst = Pt + (c * 32 + li) * CP + a * 32 + 4 * lh;
-  if (kh) {
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4)
-      *reinterpret_cast<float4*>(dst + 8 * r4) = make_float4(acc[4 * r4], acc[4 * r4 + 1], acc[4 * r4 + 2], acc[4 * r4 + 3]);
-  }
-  __syncthreads();
-  if (!kh) {
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      float4* e = reinterpret_cast<float4*>(dst + 8 * r4);
-      const float4 v = *e;
-      *e = make_float4(acc[4 * r4] + v.x, acc[4 * r4 + 1] + v.y, acc[4 * r4 + 2] + v.z, acc[4 * r4 + 3] + v.w);
-    }
-  }
-}
-
-// G (beam search): row m continues the hypothesis of row par[m] of the previous step, so its h
-// fragments and c are gathered from that row (the beams of an image are adjacent rows, so the
-// gathered 16-B fragment loads stay within the same or the neighbouring 32-row block).
-// The previous step's rescoring, run inside k_lstm<H, false, true> (greedy steps t >= 1): workgroups
-// 0 .. NR-1 rescore rows 2 bid, 2 bid + 1 of step t - 1 (k_vrescore's body, two 256-thread groups)
-// and publish each row's argmax key as one agent-scope 8-byte store into keys[t-1] (zeroed before
-// the decode, so a nonzero key is the readiness tag); the GEMM workgroups run the token-independent
-// h W_hh^T phase meanwhile and only then wait for their 64 rows' keys.  A GEMM workgroup never waits
-// on a workgroup that might not be resident: past RS_WAIT_TICKS of polling it rescores the missing
-// rows itself (the same function on the same inputs: the same key), so the launch cannot deadlock
-// whatever the dispatch order or the co-resident work of other streams.
-struct RsArgs {
-  int NR, Vp, T, t_step;
-  uint64_t wait;  // poll bound in ticks of the 100 MHz clock (RS_WAIT_TICKS; 0: AA_DECODE_RS_SELF)
-  const float* u;
-  const float4* summ;
-  const float* W;
-  const float* bias;
-  uint64_t* keys;  // keys[t-1] (B entries)
-  int64_t* ids;
-};
-template <int H>
-struct RsScratch;
-template <int H, bool PUB>
-__device__ __forceinline__ uint64_t rescore_row(int b, bool write, int t, int V, int Vp, const float* __restrict__ u,
-                                                const float4* __restrict__ summ, const float* __restrict__ W,
-                                                const float* __restrict__ bias, uint64_t* __restrict__ keys,
-                                                int64_t* __restrict__ ids, int T, int t_step, float* scr);
-constexpr uint64_t RS_WAIT_TICKS = 5000;  // 50 us of the 100 MHz constant clock
-// ring iterations (of H / 32) at which k_lstm<.., RS> DMAs the tile's keys and gathers the table rows
-constexpr int LS_RS_JK = 10, LS_RS_JG = LS_RS_JK + 3;
-// SENT = false: the baseline model's step -- the sentinel's x W_x^T gathers (sa, sb) are not issued,
-// so the gathers are LS_GATHERS - 2 ordinary loads (the ring's counted waits are told so), and the
-// cell tail is lstm_cell_tail<H, false>; s_out is not written.
-template <int H, bool G = false, bool RS = false, bool SENT = true>
-__global__ __launch_bounds__(512, 4) void k_lstm(int B, int V, const int64_t* __restrict__ tok, int tok_ld,
-                                              const float* __restrict__ table,
-                                              const float* __restrict__ xg, const bf16x8* __restrict__ hsp_in,
-                                              const float* __restrict__ c_in, const int* __restrict__ par,
-                                              const bf16x8* __restrict__ whh3,
-                                              const float* __restrict__ wgs, float* __restrict__ h_out,
-                                              bf16x8* __restrict__ hsp_out, float* __restrict__ c_out,
-                                              float* __restrict__ s_out, float* __restrict__ part, RsArgs ra) {
-  constexpr int BM = 64, CP = LS_CP, TS = 64 * LS_CP;
-  AA_TS(0, 0);
-  // the LDS-DMA ring of lstm_gemm_lds (72 KB; the summed tile and the cell tail alias it)
-  constexpr int RING_FLOATS = (LS_NB < H / 32 ? LS_NB : H / 32) * LS_STAGE * 4;
-  // + the tile's 64 tokens (+ RS: the missing-row mask and slow-path flag, the 64 keys' low words
-  // DMA'd mid-ring)
-  constexpr int LDS_FLOATS = RING_FLOATS + 64 + 4 + (RS ? 64 : 0);
-  static_assert(TS + LS_TAIL_FLOATS <= LDS_FLOATS, "tile + tail must fit in the ring");
-  __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-  constexpr int NTn = H / 16, KC = H / 16;
-  const int MT = (B + BM - 1) / BM;
-  int bid = blockIdx.x;
-  if constexpr (RS) {
-    static_assert(!G, "the fused rescoring is the greedy path's");
-    static_assert(TS + 2 * RsScratch<H>::FLOATS <= RING_FLOATS, "two rescoring scratch areas beside the tile");
-    if (bid < ra.NR) {  // rescoring role (uniform per workgroup): rows 2 bid + (t >> 8)
-      AA_TS(4, 0);
-      const int row = 2 * bid + (int)(threadIdx.x >> 8);
-      rescore_row<H, true>(row < B ? row : B - 1, row < B, threadIdx.x & 255, V, ra.Vp, ra.u, ra.summ, ra.W,
-                           ra.bias, ra.keys, ra.ids, ra.T, ra.t_step, lds + (threadIdx.x >> 8) * RsScratch<H>::FLOATS);
-      AA_TS(4, 1);
-      return;
-    }
-    bid -= ra.NR;
-  }
-  const int L = xcd_remap(bid, MT * NTn);
-  const int nt = L / MT, mt = L % MT;  // m fastest: a weight tile is shared inside an XCD
-  const int t = threadIdx.x, lane = t & 63;
-  const int m0 = mt * BM;
-  float* Pt = lds;  // [4][64][CP] partial tiles
-  const int rr = t >> 3, u0 = (t & 7) * 2, m = m0 + rr;
-  const int mc = m < B ? m : B - 1;  // rows >= B compute on row B-1 and store nothing
-  const int j = nt * 16 + u0;
-  // (token first, then the GEMM's first loads, then the token-dependent gathers: in-order vmcnt
-  //  then waits for the token alone; the asm barriers keep the compiler from reordering the loads)
-  int64_t tk = 0;
-  int* tok_lds = reinterpret_cast<int*>(lds + RING_FLOATS);
-  // the tile's 64 tokens by ONE LDS-DMA of wave 0 (the low dword of each int64 token), so that no
-  // ordinary load is outstanding beside the ring's DMAs: hipcc drains every DMA (vmcnt(0)) before
-  // the first use of an ordinary load's result while a DMA is in flight
-  // (tok == nullptr: the first step of a greedy decode, every row starts from <start> = 1: no load)
-  if (t < 64 && tok) {
-    const int r = m0 + t < B ? m0 + t : B - 1;
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(tok + (int64_t)r * tok_ld),
-                                     (__attribute__((address_space(3))) void*)tok_lds, 4, 0, 0);
-  }
-  const bf16x8* af0;
-  const bf16x8* af1;
-  int pc = mc;  // source row of c (and of h, through the fragments)
-  if constexpr (G) {
-    const int ra0 = m0 + (lane & 31), ra1 = ra0 + 32;
-    const int p0 = par[ra0 < B ? ra0 : B - 1], p1 = par[ra1 < B ? ra1 : B - 1];
-    const int hl = 32 * (lane >> 5);
-    af0 = hsp_in + (size_t)(p0 >> 5) * KC * 3 * 64 + (p0 & 31) + hl;
-    af1 = hsp_in + (size_t)(p1 >> 5) * KC * 3 * 64 + (p1 & 31) + hl;
-    pc = par[mc];
-  } else {
-    af0 = hsp_in + (size_t)(m0 / 32) * KC * 3 * 64 + lane;
-    af1 = af0 + (size_t)KC * 3 * 64;
-  }
-  const bf16x8* wf0 = whh3 + (size_t)(nt * 2) * KC * 3 * 64 + lane;
-  const bf16x8* wf1 = wf0 + (size_t)KC * 3 * 64;
-  // epilogue gathers behind the first GEMM loads: token -> table row, x_g, c, W_g/W_s slice
-  float2 ta[4], xa[4], sa, sb, cprev;
-  if constexpr (!SENT) sa = sb = make_float2(0.f, 0.f);  // (not gathered, not read)
-  constexpr int NGATH = SENT ? LS_GATHERS : LS_GATHERS - 2;  // ordinary loads of gathers()
-  constexpr int NWS4 = (SENT ? 2 : 1) * P * 4;               // float4s of the tile's W_g (/ W_s) slice in use
-  float4 wsv;
-  const int N5 = 5 * H;
-  // the token's table row (5 loads)
-  auto gather_table = [&] {
-    tk = tk < 0 ? 0 : (tk >= V ? V - 1 : tk);
-    const float* trow = table + tk * N5;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) ta[g] = *reinterpret_cast<const float2*>(trow + nt * 64 + g * 16 + u0);
-    if constexpr (SENT) sa = *reinterpret_cast<const float2*>(trow + 4 * H + j);
-  };
-  // the token-independent operands: x_g, c, the W_g / W_s slice (7 loads)
-  auto gather_x = [&] {
-    const float* xrow = xg + (int64_t)mc * N5;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) xa[g] = *reinterpret_cast<const float2*>(xrow + nt * 64 + g * 16 + u0);
-    if constexpr (SENT) sb = *reinterpret_cast<const float2*>(xrow + 4 * H + j);
-    cprev = *reinterpret_cast<const float2*>(c_in + (int64_t)pc * H + j);
-    // W_g / W_s slice: wgs[tile] is [98][16] (j-major); thread t < 392 takes float4 t
-    const float4* src = reinterpret_cast<const float4*>(wgs + (int64_t)nt * 2 * P * 16);
-    wsv = src[t < NWS4 ? t : NWS4 - 1];
-  };
-  auto gathers = [&] {
-    gather_table();
-    gather_x();
-  };
-  // token first (oldest), then the ring's first three stages, then -- once the token is in --
-  // the token-dependent gathers (exactly LS_GATHERS loads, counted by the ring's waits)
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (RS) {
-    // The GEMM phase needs no token.  At ring iteration LS_RS_JK wave 0 DMAs the low words of the
-    // tile's 64 keys into LDS (agent-coherent sc1 reads of the granules the rescoring workgroups
-    // publish: a non-zero low word = published, it is 0xFFFFFFFF - token), and at iteration LS_RS_JG
-    // -- that DMA landed -- every thread takes its row's token if published and issues all twelve
-    // gathers (table row, x_g, c, W_g / W_s slice: issued there rather than with the first stages, so
-    // they are not live across the whole ring), which land under the last iterations.  Rows not yet published then are polled / rescored after the ring, as before,
-    // and only their table rows are gathered again.
-    uint32_t* klo = reinterpret_cast<uint32_t*>(lds + RING_FLOATS + 64 + 4);
-    // (hooks scaled to the ring's H / 32 iterations; rings under 12 iterations: gathers after the ring)
-    constexpr int NI = H / 32, JK = NI >= 12 ? LS_RS_JK * NI / 16 : -1, JG = JK < 0 ? -1 : JK + (LS_RS_JG - LS_RS_JK);
-    lstm_gemm_lds<H, 0, JK, JG, NGATH>(
-        af0, af1, wf0, wf1, reinterpret_cast<bf16x8*>(lds), Pt, [] {},
-        [&] {
-          if (t < 64) {
-            const int r = m0 + t < B ? m0 + t : B - 1;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(ra.keys + r),
-                                             (__attribute__((address_space(3))) void*)klo, 4, 0, 16 /* sc1 */);
-          }
-        },
-        [&] {
-          const uint32_t kl = klo[rr];
-          tk = kl != 0u ? (int64_t)(0xFFFFFFFFu - kl) : 0;  // not yet published: gathered again below
-          gathers();
-        });
-    AA_TS(0, 5);
-    __syncthreads();
-    uint64_t* miss = reinterpret_cast<uint64_t*>(lds + RING_FLOATS + 64);
-    if (t < 64) {
-      const uint32_t kl = JK < 0 ? 0u : klo[t];
-      if (__all(kl != 0u)) {  // wave-uniform: every row was published by iteration JK
-        if (t == 0) miss[0] = 0, miss[1] = 0;
-      } else {
-        const int r = m0 + t < B ? m0 + t : B - 1;
-        uint64_t k = __hip_atomic_load(ra.keys + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t t0 = wall_clock64();
-        while (!__all(k != 0)) {  // wave-uniform: bounded poll of the 8-byte granules
-          if (wall_clock64() - t0 > ra.wait) break;
-          __builtin_amdgcn_s_sleep(1);
-          if (k == 0) k = __hip_atomic_load(ra.keys + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        tok_lds[t] = (int)key_token(k);
-        const uint64_t mb = __ballot(k == 0);
-        if (t == 0) miss[0] = mb, miss[1] = 1;
-      }
-    }
-    __syncthreads();
-    if (miss[1]) {  // (workgroup-uniform) some key came after iteration JK: the slow path
-      uint64_t mb = miss[0];
-      // rows not yet published: rescored here, two at a time (the tile's Pt stays below the scratch)
-      while (mb) {
-        const int i0 = __builtin_ctzll(mb);
-        mb &= mb - 1;
-        const int i1 = mb ? __builtin_ctzll(mb) : i0;
-        if (mb) mb &= mb - 1;
-        const int i = (t >> 8) ? i1 : i0;
-        const int r = m0 + i < B ? m0 + i : B - 1;
-        const uint64_t k = rescore_row<H, true>(r, (t >> 8) == 0 || i1 != i0, t & 255, V, ra.Vp, ra.u, ra.summ, ra.W,
-                                                ra.bias, ra.keys, ra.ids, ra.T, ra.t_step,
-                                                lds + TS + (t >> 8) * RsScratch<H>::FLOATS);
-        if ((t & 255) == 0) tok_lds[i] = (int)key_token(k);
-        __syncthreads();
-      }
-      // every gather again (the mid-ring values are dead on this path, so they are not kept live
-      // across the rescoring above)
-      tk = tok_lds[rr];
-      gathers();
-    }
-  } else {
-    lstm_gemm_lds<H, NGATH>(af0, af1, wf0, wf1, reinterpret_cast<bf16x8*>(lds), Pt, [&] {
-      // wave 0's token DMA is older than its ring DMAs: retire it, then every wave reads its row's
-      if (t < 64) vm_wait(LS_NPW * (LS_NB < H / 32 ? LS_NB : H / 32));
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      tk = tok ? tok_lds[rr] : 1;
-      gathers();
-      asm volatile("" ::: "memory");
-    });
-  }
-  AA_TS(0, 1);
-  __syncthreads();
-  float gate[4][2];
-  {
-    const float* cr = Pt + rr;  // column j of the summed tile at cr[j * CP]
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) gate[g][q] = cr[(16 * g + u0 + q) * CP] + ((&ta[g].x)[q] + (&xa[g].x)[q]);
-  }
-  AA_TS(0, 2);
-  lstm_cell_tail<H, SENT>(B, m0, nt, gate, sa, sb, cprev, wsv, lds + TS, h_out, hsp_out, c_out, s_out, part);
-  AA_TS(0, 4);
-}
 
 __global__ void k_fill_tok(int64_t* __restrict__ tok, int B, int64_t v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) tok[i] = v;
-}
-// Start of a greedy decode: <start> tokens, and (exact vocab stage) the [T][B] argmax keys that
-// k_vocab accumulates by atomicMax cleared -- by memory-side stores, like the atomics that follow (a
-// plain store's line would stay in this XCD's L2)
-__global__ void k_decode_init(int64_t* __restrict__ tok, int B, int64_t v, uint64_t* __restrict__ keys, int n) {
-  const int i0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-  for (int i = i0; i < B; i += stride) tok[i] = v;
-  if (keys)
-    for (int i = i0; i < n; i += stride) __hip_atomic_store(keys + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __global__ void k_key_ids(const uint64_t* __restrict__ keys, int B, int64_t* __restrict__ ids, int ld) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1545,8 +243,8 @@ __global__ __launch_bounds__(256) void k_atten(int B, int NTL, int kdiv, const f
   }
 }
 
-// The arithmetic of one attention row once its operands are in registers, shared by k_atten5 and
-// the attention role of the fused launch k_lstm<.., AT> (so the two produce the same bits).  Thread t
+// The arithmetic of one attention row once its operands are in registers, shared by k_atten5's
+// forms with and without the sentinel (the same operations in the same order).  Thread t
 // (512 per row): projection group grp = t >> 7, output jp = t & 127 (pv: its H/64 tile partials, tiles
 // grp, grp + 4, ...); score item k = t >> 3, lane q = t & 7 (vwr / whr: its 7 terms j = q + 8 i);
 // context dimensions t + 512 i (hv, sv; V through vget(i, kk)).  The 32 projection partials are summed
@@ -1895,18 +593,6 @@ __global__ __launch_bounds__(512) void k_atten5b(const float* __restrict__ h_new
 // 128x128 tile, then per (row, 32-column granule g) with the granule's bound E (see screen_bound):
 //   summ[row][g] = {max_n A_n - E, max_n A_n + E, second largest A_n + E, arg-max column}.
 // ---------------------------------------------------------------------------------------------
-// Partner exchange for the screen epilogue's butterfly over the 32 lanes of a column block: level
-// M pairs each lane with one whose index differs in bit M and agrees in the bits above it --
-// M = 16: ds_swizzle xor 16; 8: DPP row_mirror (i <-> 15 - i); 4: row_half_mirror (i <-> 7 - i);
-// 2, 1: DPP quad_perm xor 2 / xor 1.  No LDS traffic except the one swizzle level.
-template <int M>
-__device__ __forceinline__ uint32_t partner(uint32_t v) {
-  if constexpr (M == 16) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
-  else if constexpr (M == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);
-  else if constexpr (M == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
-  else if constexpr (M == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
-  else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
-}
 
 // One transposing butterfly step: a lane carrying M rows keeps half of them (the upper half if
 // bit M of its lane index is set) merged with its partner's copy of the same rows.  Merge: top-2
@@ -2342,137 +1028,6 @@ __global__ __launch_bounds__(SC8_NT) void k_vscreen8(int B, int V, int Vp, const
   AA_TS(2, 2);
 }
 
-// Exact fp32 logit of one column, computed by a group of 8 lanes (lane8 = 0..7): lane8 j runs the
-// fma chain of partial j (K-steps [j*per, (j+1)*per) of 32, in the MFMA k order: pairs (s, 16+s)),
-// then the fixed tree ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)) over xor-1/2/4 shuffles, then + bias.
-// Bit-identical to k_vocab (gemm_mainloop_np<.., NP_VOCAB>).  All 8 lanes return the logit.
-// u is read from LDS (urow), w straight from memory (each lane 4*32*per contiguous bytes).
-template <int HC = 0>  // HC > 0: H known at compile time (the K steps' loads issue together)
-__device__ __forceinline__ float exact_logit8(const float* __restrict__ urow, const float* __restrict__ wrow, int H,
-                                              float b, int lane8) {
-  const int per = (HC > 0 ? HC : H) / (32 * NP_VOCAB);
-  const int k0 = lane8 * per * 32;
-  float acc = 0.f;
-  constexpr int KU = HC > 0 ? HC / (32 * NP_VOCAB) : 1;
-#pragma unroll KU
-  for (int ks = 0; ks < per; ++ks) {
-    float4 w[8], u[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      w[q] = *reinterpret_cast<const float4*>(wrow + k0 + 32 * ks + 4 * q);
-      u[q] = *reinterpret_cast<const float4*>(urow + k0 + 32 * ks + 4 * q);
-    }
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      acc = __builtin_fmaf(f4c(u[s >> 2], s & 3), f4c(w[s >> 2], s & 3), acc);
-      acc = __builtin_fmaf(f4c(u[4 + (s >> 2)], s & 3), f4c(w[4 + (s >> 2)], s & 3), acc);
-    }
-  }
-  acc = acc + __shfl_xor(acc, 1, 64);
-  acc = acc + __shfl_xor(acc, 2, 64);
-  acc = acc + __shfl_xor(acc, 4, 64);
-  return acc + b;
-}
-
-// ---------------------------------------------------------------------------------------------
-// D3b (greedy path): one workgroup (4 waves) per row.  M = max over granules of lbmax; candidates
-// = idx1 of granules with ub1 >= M, plus every column of granules with ub2 >= M (two candidates in
-// one granule).  32 candidates are scored per pass (8 lanes each, exact_logit8); first-index argmax
-// -> keys[row], ids[row, t].  A list longer than RS_CAP falls back to every column (correct, slow).
-// (Tried: re-screening a ub2 >= M granule's 32 columns in bf16 here, sequentially or 64 columns per
-// round, and scoring only those within the bound: fewer exact logits, but slower overall.  Also
-// tried: each wave reading the W row of its best granule's arg-max column before the barriers, as a
-// cache warm-up for the likely winner: k_vrescore 9.95 -> 10.4 us by events in A/B.)
-// ---------------------------------------------------------------------------------------------
-constexpr int RS_NT = 256, RS_NW = RS_NT / 64;
-// LDS scratch of one rescored row (floats): u row, candidate list, count, wave maxima, wave keys
-template <int H>
-struct RsScratch {
-  static constexpr int URow = 0, Cand = H, NCand = H + RS_CAP, WMax = NCand + 4, WBest = WMax + RS_NW + 4,
-                       FLOATS = WBest + 2 * RS_NW;
-  static_assert(H % 4 == 0 && WBest % 2 == 0, "16-B u row, 8-B keys");
-};
-// The rescoring of one row by RS_NT threads (t = 0 .. RS_NT-1 of the calling group; every thread of
-// the workgroup reaches the same three barriers): k_vrescore's body.  PUB: the key is stored by an
-// agent-scope atomic store (a write-through granule that k_lstm<.., RS> polls within its launch);
-// write = false computes without storing (a padding group that only keeps the barrier count).
-// Returns the row's key in every thread.
-template <int H, bool PUB>
-__device__ __forceinline__ uint64_t rescore_row(int b, bool write, int t, int V, int Vp, const float* __restrict__ u,
-                                                const float4* __restrict__ summ, const float* __restrict__ W,
-                                                const float* __restrict__ bias, uint64_t* __restrict__ keys,
-                                                int64_t* __restrict__ ids, int T, int t_step, float* scr) {
-  typedef RsScratch<H> S;
-  float* urow = scr + S::URow;
-  int* cand = reinterpret_cast<int*>(scr + S::Cand);
-  int& ncand = *reinterpret_cast<int*>(scr + S::NCand);
-  float* wmax = scr + S::WMax;
-  uint64_t* wbest = reinterpret_cast<uint64_t*>(scr + S::WBest);
-  const int lane = t & 63, w = t >> 6;
-  const int NTn = Vp / VS_TILE;
-  for (int d = 4 * t; d < H; d += 4 * RS_NT) *reinterpret_cast<float4*>(&urow[d]) = *reinterpret_cast<const float4*>(u + (int64_t)b * H + d);
-  if (t == 0) ncand = 0;
-  const float4* sm = summ + (int64_t)b * NTn;
-  // a thread's first two summaries stay in registers between the max and the selection (any
-  // further ones are read again)
-  float4 s0 = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f), s1 = s0;
-  if (t < NTn) s0 = sm[t];
-  if (t + RS_NT < NTn) s1 = sm[t + RS_NT];
-  float mlb = fmaxf(s0.x, s1.x);
-  for (int i = t + 2 * RS_NT; i < NTn; i += RS_NT) mlb = fmaxf(mlb, sm[i].x);
-  mlb = wave_max(mlb);
-  if (lane == 0) wmax[w] = mlb;
-  __syncthreads();
-  AA_TS(3, 1);
-  mlb = wmax[0];
-#pragma unroll
-  for (int i = 1; i < RS_NW; ++i) mlb = fmaxf(mlb, wmax[i]);
-  auto select = [&](const float4& s, int i) {
-    if (s.z >= mlb) {  // >= 2 candidates in this granule: take all of its columns
-      const int pos = atomicAdd(&ncand, VS_TILE);
-      for (int c = 0; c < VS_TILE; ++c)
-        if (pos + c < RS_CAP) cand[pos + c] = i * VS_TILE + c;
-    } else if (s.y >= mlb) {
-      const int pos = atomicAdd(&ncand, 1);
-      if (pos < RS_CAP) cand[pos] = __float_as_int(s.w);
-    }
-  };
-  if (t < NTn) select(s0, t);
-  if (t + RS_NT < NTn) select(s1, t + RS_NT);
-  for (int i = t + 2 * RS_NT; i < NTn; i += RS_NT) select(sm[i], i);
-  __syncthreads();
-  AA_TS(3, 2);
-  // an empty list (summaries that are all NaN) or an overflowing one: every column; the key starts at
-  // the lowest non-zero key, so a published key is never 0 (0 = "not yet published" for k_lstm<.., RS>)
-  const bool all = ncand > RS_CAP || ncand == 0;
-  const int n = all ? V : ncand;
-  const int g = t >> 3, lane8 = t & 7;
-  uint64_t best = argmax_key(-INFINITY, V - 1);
-  for (int i = g; i < n; i += RS_NT / 8) {
-    int col = all ? i : cand[i];
-    const bool ok = col < V;
-    col = ok ? col : V - 1;
-    // (the K steps' loads one after the other: measured faster here than all issued together)
-    const float x = exact_logit8(urow, W + (int64_t)col * H, H, bias[col], lane8);
-    if (ok) {
-      const uint64_t k = argmax_key(x, col);
-      best = k > best ? k : best;
-    }
-  }
-  best = wave_max_u64(best);
-  if (lane == 0) wbest[w] = best;
-  __syncthreads();
-  uint64_t k = wbest[0];
-#pragma unroll
-  for (int i = 1; i < RS_NW; ++i) k = wbest[i] > k ? wbest[i] : k;
-  if (t == 0 && write) {
-    if (ids) ids[(int64_t)b * T + t_step] = key_token(k);
-    if constexpr (PUB) __hip_atomic_store(keys + b, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else keys[b] = k;
-  }
-  return k;
-}
-
 template <int H>
 __global__ __launch_bounds__(RS_NT) void k_vrescore(int B, int V, int Vp, const float* __restrict__ u,
                                                   const float4* __restrict__ summ, const float* __restrict__ W,
@@ -2503,177 +1058,12 @@ __global__ __launch_bounds__(256) void k_logits_at(int H, int V, const float* __
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// D3 (exact path): logits = u W_m^T + b_m (AdaptiveBlock.mlp, adaptive_attention.py:132) with the
-// argmax of sampler (:201) fused into the epilogue: per-row max over the tile's columns by 64-bit
-// keys (lane shuffles, then LDS across the two column waves), one atomicMax per row per workgroup.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_vocab(int B, int H, int V, int Vp, int ld, const float* __restrict__ u,
-                                               const float* __restrict__ W, const float* __restrict__ bias,
-                                               float* __restrict__ scores, uint64_t* __restrict__ keys) {
-  constexpr int BM = 64, BN = 64;
-  __shared__ __attribute__((aligned(16))) float lds[Tile<BM, BN>::LDS_FLOATS];
-  const int MT = (B + BM - 1) / BM, NTn = Vp / BN;
-  const int L = xcd_remap(blockIdx.x, MT * NTn);
-  const int nt = L / MT, mt = L % MT;
-  ARowMajor al{u, H, mt * BM, B};
-  WRowMajor wl{W, H, nt * BN};
-  floatx16 acc[NP_VOCAB][1][1];
-  gemm_mainloop_np<BM, BN, NP_VOCAB>(al, wl, H / BK, lds, acc);
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-  const int col = nt * BN + wn * 32 + (lane & 31);
-  const bool valid = col < V;
-  const float bv = bias[col];
-  uint64_t best[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float p01 = acc[0][0][0][r] + acc[1][0][0][r], p23 = acc[2][0][0][r] + acc[3][0][0][r];
-    const float p45 = acc[4][0][0][r] + acc[5][0][0][r], p67 = acc[6][0][0][r] + acc[7][0][0][r];
-    const float x = ((p01 + p23) + (p45 + p67)) + bv;
-    const int row = mt * BM + wm * 32 + acc_row(r, lane);
-    if (scores && valid && row < B) scores[(int64_t)row * ld + col] = x;
-    uint64_t k = valid ? argmax_key(x, col) : 0ull;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      const uint64_t y = shfl_xor_u64(k, o);
-      k = y > k ? y : k;
-    }
-    best[r] = k;
-  }
-  uint64_t* red = reinterpret_cast<uint64_t*>(lds);  // [2 column waves][64 rows]
-  if ((lane & 31) == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wn * 64 + wm * 32 + acc_row(r, lane)] = best[r];
-  }
-  __syncthreads();
-  if (t < 64) {
-    const uint64_t a = red[t], c = red[64 + t];
-    const int row = mt * BM + t;
-    if (row < B && keys) atomicMax(reinterpret_cast<unsigned long long*>(keys + row), (unsigned long long)(a > c ? a : c));
-  }
-}
-
 // ids [B][T] from the argmax keys [T][ldk] (ldk = the whole batch when B is a lane's row block)
 __global__ void k_finalize(const uint64_t* __restrict__ keys, int B, int T, int64_t* __restrict__ ids, int ldk) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * T) return;
   const int b = (int)(i / T), t = (int)(i % T);
   ids[i] = key_token(keys[(int64_t)t * ldk + b]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// packing / synthetic data
-// ---------------------------------------------------------------------------------------------
-// Gate-interleaved LSTM tiles: packed row r = tile*64 + gate*16 + unit  <-  reference row
-// gate*H + tile*16 + unit of W_ih / W_hh / biases (gate order i, f, g, o); rows 4H + j of the
-// emb / v_g parts are W_x row j (sentinel).
-__global__ void k_pack_lstm(const float* __restrict__ w_ih, const float* __restrict__ w_hh, const float* __restrict__ b_ih,
-                            const float* __restrict__ b_hh, const float* __restrict__ w_x, int E, int H,
-                            float* __restrict__ whh, float* __restrict__ wemb, float* __restrict__ wvg, float* __restrict__ bias5) {
-  const int r = blockIdx.x;  // 0 .. 5H-1
-  const int KX = 2 * E;
-  if (r < 4 * H) {
-    const int tile = r / 64, g = (r % 64) / 16, un = r % 16;
-    const int src = g * H + tile * 16 + un;
-    for (int k = threadIdx.x; k < E; k += blockDim.x) {
-      wemb[(int64_t)r * E + k] = w_ih[(int64_t)src * KX + k];
-      wvg[(int64_t)r * E + k] = w_ih[(int64_t)src * KX + E + k];
-    }
-    for (int k = threadIdx.x; k < H; k += blockDim.x) whh[(int64_t)r * H + k] = w_hh[(int64_t)src * H + k];
-    if (threadIdx.x == 0) bias5[r] = b_ih[src] + b_hh[src];
-  } else if (w_x) {  // (a baseline model has no sentinel: its fifth block stays zero)
-    const int j = r - 4 * H;
-    for (int k = threadIdx.x; k < E; k += blockDim.x) {
-      wemb[(int64_t)r * E + k] = w_x[(int64_t)j * KX + k];
-      wvg[(int64_t)r * E + k] = w_x[(int64_t)j * KX + E + k];
-    }
-    if (threadIdx.x == 0) bias5[r] = 0.f;
-  }
-}
-
-// wgs[tile][j][u] = (j < 49 ? W_g[j] : W_s[j - 49])[tile*16 + u]
-// W_a split into three bf16 planes in MFMA-fragment order (see k_enc_v3): block = (nb, kc), lane l
-// -> W[32 nb + (l & 31)][16 kc + 8 (l >> 5) + j], planes q = 0, 1, 2 at out[((nb KC + kc) 3 + q) 64 + l].
-__global__ void k_pack_w3(const float* __restrict__ w, int C, bf16x8* __restrict__ out) {
-  const int KC = C / 16, nb = blockIdx.x / KC, kc = blockIdx.x % KC, l = threadIdx.x;
-  const float* src = w + (int64_t)(32 * nb + (l & 31)) * C + 16 * kc + 8 * (l >> 5);
-  bf16x8 h, m, lo;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 a, b, c;
-    split3(src[j], a, b, c);
-    h[j] = a; m[j] = b; lo[j] = c;
-  }
-  bf16x8* o = out + ((size_t)blockIdx.x * 3) * 64 + l;
-  o[0] = h;
-  o[64] = m;
-  o[128] = lo;
-}
-
-// W_a split into three bf16 planes in 16x16x32 B-fragment order (see k_enc_v4): block = (nb, kc),
-// lane l -> W[16 nb + (l & 15)][32 kc + 8 (l >> 4) + j], planes at out[((nb KC + kc) 3 + q) 64 + l].
-__global__ void k_pack_w4(const float* __restrict__ w, int C, bf16x8* __restrict__ out) {
-  const int KC = C / 32, nb = blockIdx.x / KC, kc = blockIdx.x % KC, l = threadIdx.x;
-  const float* src = w + (int64_t)(16 * nb + (l & 15)) * C + 32 * kc + 8 * (l >> 4);
-  bf16x8 h, m, lo;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 a, b, c;
-    split3(src[j], a, b, c);
-    h[j] = a; m[j] = b; lo[j] = c;
-  }
-  bf16x8* o = out + ((size_t)blockIdx.x * 3) * 64 + l;
-  o[0] = h;
-  o[64] = m;
-  o[128] = lo;
-}
-
-__global__ void k_pack_wgs(const float* __restrict__ wg, const float* __restrict__ ws, int H, float* __restrict__ out) {
-  const int tile = blockIdx.x;
-  // (ws == nullptr: a baseline model, the W_s half stays zero)
-  for (int i = threadIdx.x; i < (ws ? 2 : 1) * P * 16; i += blockDim.x) {
-    const int j = i / 16, u = i % 16;
-    const float* src = j < P ? wg + (int64_t)j * H : ws + (int64_t)(j - P) * H;
-    out[(int64_t)tile * 2 * P * 16 + i] = src[tile * 16 + u];
-  }
-}
-
-// bf16 copy of W_m (zero rows beyond V) and, for the screen bound, the row norms ||w_n||_2 (wn[n])
-// and ||w_n - bf16(w_n)||_2 (wn[Vp + n]), each inflated by 1e-4 over its fp32 rounding (a sum of
-// H <= 1024 squares: relative error <= gamma_1024 ~ 6.1e-5, then the square root).
-__global__ void k_pack_mlp(const float* __restrict__ w, int V, int H, int Vp, uint16_t* __restrict__ wb,
-                           float* __restrict__ wn) {
-  const int n = blockIdx.x, lane = threadIdx.x;  // 64 threads
-  float s = 0.f, sd = 0.f;
-  for (int k = lane; k < H; k += 64) {
-    const float x = n < V ? w[(int64_t)n * H + k] : 0.f;
-    const uint16_t xb = f2bf(x);
-    wb[frag_off(n, k, H)] = xb;
-    const float d = x - __uint_as_float((uint32_t)xb << 16);  // exact (Sterbenz)
-    s = __builtin_fmaf(x, x, s);
-    sd = __builtin_fmaf(d, d, sd);
-  }
-  s = wave_sum(s);
-  sd = wave_sum(sd);
-  if (lane == 0) {
-    wn[n] = sqrtf(s) * 1.0001f;
-    wn[Vp + n] = sqrtf(sd) * 1.0001f;
-  }
-}
-
-// Per 32-column granule of the vocab: (max ||w_n||, max |b_n|, max ||w_n - bf16(w_n)||, 0) for the
-// screen's bound.
-__global__ void k_pack_gs(const float* __restrict__ wn, const float* __restrict__ b, int Vp, float4* __restrict__ gs) {
-  const int g = blockIdx.x, l = threadIdx.x;  // 64 threads, lanes >= 32 mirror 0..31
-  const int n = g * VS_TILE + (l & (VS_TILE - 1));
-  const float mw = wave_max(wn[n]), mb = wave_max(fabsf(b[n])), md = wave_max(wn[Vp + n]);
-  if (l == 0) gs[g] = make_float4(mw, mb, md, 0.f);
-}
-
-__device__ __forceinline__ uint64_t splitmix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 __global__ void k_synth_uniform(float* __restrict__ dst, int64_t n, uint64_t key, int64_t start, double lo, double span, int plain) {
@@ -2691,19 +1081,20 @@ __global__ void k_synth_uniform(float* __restrict__ dst, int64_t n, uint64_t key
 // =============================================================================================
 using namespace aa;
 
-static int launch_status() { return aa_launch_status(); }
-static bool al16(const void* p) { return aa_al16(p); }
-
-static void gemm_bias(const float* A, int lda, int M, const float* W, int ldw, int N, int K, const float* bias, float* C,
-                      int64_t ldc, hipStream_t s) {
-  const int MT = (M + 63) / 64, NTn = N / 64;
-  hipLaunchKernelGGL(k_gemm_bias, dim3(MT * NTn), dim3(256), 0, s, A, lda, M, W, ldw, N, K, bias, C, ldc);
-}
 
 int aa_abi_version(void) { return AA_ABI_VERSION; }
 #ifdef AA_TS_ENABLE
+namespace aa {
+template <int H>
+int ts_set_lstm(void* buf);  // aa_lstm.hip: each k_lstm object's copy of the pointer
+}
 extern "C" __attribute__((visibility("default"))) int aa_ts_setup(void* buf) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(aa_ts_buf), &buf, sizeof(buf));
+  int rc = ts_set_local(buf);
+  if (!rc) rc = ts_set_lstm<256>(buf);
+  if (!rc) rc = ts_set_lstm<512>(buf);
+  if (!rc) rc = ts_set_lstm<768>(buf);
+  if (!rc) rc = ts_set_lstm<1024>(buf);
+  return rc;
 }
 #endif
 
@@ -2732,264 +1123,16 @@ size_t aa_packed_bytes(const aa_dims* d) {
   return make_layout(*d).total_floats * sizeof(float);
 }
 
-static int check_model(const aa_model* m, Layout* L) {
-  if (!m || !m->packed) return AA_ERR_NULL;
-  int rc = aa_check_dims(&m->dims);
-  if (rc) return rc;
-  *L = make_layout(m->dims);
-  if (m->packed_bytes < L->total_floats * sizeof(float)) return AA_ERR_BUFFER;
-  if (((uintptr_t)m->packed & 255u) != 0) return AA_ERR_ALIGN;
-  return AA_OK;
-}
 
-int aa_pack_weights(const aa_model* m, const aa_ref_weights* w, aa_stream_t stream) {
-  Layout L;
-  int rc = check_model(m, &L);
-  if (rc) return rc;
-  if (!w) return AA_ERR_NULL;
-  const float* req[] = {w->enc_affine_a_w, w->enc_affine_a_b, w->enc_affine_b_w, w->enc_affine_b_b,
-                        w->enc_affine_h0_w, w->enc_affine_h0_b, w->enc_affine_c0_w, w->enc_affine_c0_b,
-                        w->embed_w, w->lstm_w_ih, w->lstm_w_hh, w->lstm_b_ih, w->lstm_b_hh,
-                        w->att_affine_v_w, w->att_affine_g_w, w->att_affine_h_w, w->mlp_w, w->mlp_b};
-  for (const float* p : req)
-    if (!p) return AA_ERR_NULL;
-  // both sentinel weights NULL: a baseline (no-sentinel) model, whose sentinel blocks stay zero; one
-  // without the other is an error
-  const bool baseline = !w->sent_affine_x_w && !w->att_affine_s_w;
-  if (!baseline && (!w->sent_affine_x_w || !w->att_affine_s_w)) return AA_ERR_NULL;
-  if (!al16(w->embed_w)) return AA_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  float* base = static_cast<float*>(m->packed);
-  const int E = L.E, H = L.H, V = L.V, C = L.C;
-  AA_TRY(hipMemsetAsync(base, 0, L.total_floats * sizeof(float), s));
-  auto cp = [&](const float* src, size_t off, size_t n) {
-    return hipMemcpyAsync(base + off, src, n * sizeof(float), hipMemcpyDeviceToDevice, s);
-  };
-  AA_TRY(cp(w->enc_affine_a_w, L.enc_a_w, (size_t)H * C));
-  AA_TRY(cp(w->enc_affine_a_b, L.enc_a_b, H));
-  AA_TRY(cp(w->enc_affine_b_w, L.heads_w, (size_t)E * C));
-  AA_TRY(cp(w->enc_affine_h0_w, L.heads_w + (size_t)E * C, (size_t)H * C));
-  AA_TRY(cp(w->enc_affine_c0_w, L.heads_w + (size_t)(E + H) * C, (size_t)H * C));
-  AA_TRY(cp(w->enc_affine_b_b, L.heads_b, E));
-  AA_TRY(cp(w->enc_affine_h0_b, L.heads_b + E, H));
-  AA_TRY(cp(w->enc_affine_c0_b, L.heads_b + E + H, H));
-  AA_TRY(cp(w->att_affine_v_w, L.wv, (size_t)P * H));  // rows 49..63 stay zero
-  AA_TRY(cp(w->att_affine_g_w, L.wg, (size_t)P * H));
-  if (!baseline) AA_TRY(cp(w->att_affine_s_w, L.ws, (size_t)P * H));
-  AA_TRY(cp(w->att_affine_h_w, L.wh, P));
-  AA_TRY(cp(w->mlp_w, L.mlp_w, (size_t)V * H));        // rows V..Vp-1 stay zero
-  AA_TRY(cp(w->mlp_b, L.mlp_b, V));
-  hipLaunchKernelGGL(k_pack_lstm, dim3(L.N5), dim3(256), 0, s, w->lstm_w_ih, w->lstm_w_hh, w->lstm_b_ih, w->lstm_b_hh,
-                     w->sent_affine_x_w, E, H, base + L.whh, base + L.wemb, base + L.wvg, base + L.bias5);
-  // table[v] = embed[v] . [W_ih(emb part) (packed gate order); W_x(emb part)]^T
-  gemm_bias(w->embed_w, E, V, base + L.wemb, E, L.N5, E, nullptr, base + L.table, L.N5, s);
-  hipLaunchKernelGGL(k_pack_mlp, dim3(L.Vp), dim3(64), 0, s, base + L.mlp_w, V, H, L.Vp,
-                     reinterpret_cast<uint16_t*>(base + L.mlp_wb), base + L.mlp_wn);
-  hipLaunchKernelGGL(k_pack_gs, dim3(L.Vp / VS_TILE), dim3(64), 0, s, base + L.mlp_wn, base + L.mlp_b, L.Vp,
-                     reinterpret_cast<float4*>(base + L.mlp_gs));
-  hipLaunchKernelGGL(k_pack_wgs, dim3(H / 16), dim3(256), 0, s, w->att_affine_g_w, w->att_affine_s_w, H, base + L.wgs);
-  hipLaunchKernelGGL(k_pack_w3, dim3((H / 32) * (C / 16)), dim3(64), 0, s, w->enc_affine_a_w, C,
-                     reinterpret_cast<bf16x8*>(base + L.enc_w3));
-  hipLaunchKernelGGL(k_pack_w3, dim3((4 * H / 32) * (H / 16)), dim3(64), 0, s, base + L.whh, H,
-                     reinterpret_cast<bf16x8*>(base + L.whh3));
-  hipLaunchKernelGGL(k_pack_w3, dim3((L.Vp / 32) * (H / 16)), dim3(64), 0, s, base + L.mlp_w, H,
-                     reinterpret_cast<bf16x8*>(base + L.mlp_w3));
-  hipLaunchKernelGGL(k_pack_w4, dim3((H / 16) * (C / 32)), dim3(64), 0, s, w->enc_affine_a_w, C,
-                     reinterpret_cast<bf16x8*>(base + L.enc_w4));
-  hipLaunchKernelGGL(k_pack_w4, dim3((L.NHp / 16) * (C / 32)), dim3(64), 0, s, base + L.heads_w, C,
-                     reinterpret_cast<bf16x8*>(base + L.heads_w4));
-  if (E % 32 == 0)
-    hipLaunchKernelGGL(k_pack_w4, dim3((L.N5 / 16) * (E / 32)), dim3(64), 0, s, base + L.wvg, E,
-                       reinterpret_cast<bf16x8*>(base + L.wvg4));
-  if (H % 32 == 0)
-    hipLaunchKernelGGL(k_pack_w4, dim3((PP / 16) * (H / 32)), dim3(64), 0, s, base + L.wv, H,
-                       reinterpret_cast<bf16x8*>(base + L.wv4));
-  return launch_status();
-}
 
-static inline void rec(aa_event_t* arr, int i, hipStream_t s) {
-  if (arr) (void)hipEventRecord((hipEvent_t)arr[i], s);
-}
-// Per-kernel timing hook (aa_trace): with an event array, the pair (I, I + 1) is handed to the launch
-// itself (hipExtLaunchKernel's start / stop events), which stamps it with the dispatch's own begin /
-// end timestamps -- the figures rocprofv3's kernel trace reads -- and no event packet sits between the
-// timed launches.  (Round 4 recorded events around each launch: ~1.5-3 us per launch of skew, and a
-// traced decode 1.46x slower than an untraced one.)  Kernel names with commas go in parentheses.
-#define AA_TLAUNCH(EV, I, K, G, BL, SH, S, ...)                                                              \
-  do {                                                                                                       \
-    aa_event_t* ev_ = (EV);                                                                                  \
-    if (ev_)                                                                                                 \
-      hipExtLaunchKernelGGL(K, G, BL, SH, S, (hipEvent_t)ev_[(I)], (hipEvent_t)ev_[(I) + 1], 0u, __VA_ARGS__); \
-    else                                                                                                     \
-      hipLaunchKernelGGL(K, G, BL, SH, S, __VA_ARGS__);                                                      \
-  } while (0)
-
-// Encoder tail.  With an aux stream, the a_g branch (k_avgpool -> k_enc_heads -> x_g GEMM: HBM- and
-// latency-bound) runs beside the V branch (k_enc_v3 -> VWv GEMM: MFMA-bound); both read only the
-// features, and `s` waits for aux before returning.
-// the encoder's V GEMM runs on k_enc_v4 (which also writes the compressed V when asked)
-static bool enc_v4(const Layout& L, int32_t flags) {
-  return !(flags & AA_DECODE_FP32_ENCODER) && (L.H == 512 || L.H == 256) && L.C <= E4_MAXC;
-}
-// x_g and VWv on k_gemm3 (bf16x3) unless an fp32-MFMA encoder was asked for; K % 256 == 0 (4 waves)
-static bool gemm3_ok(int32_t flags, int K) {
-  return !(flags & AA_DECODE_FP32_ENCODER) && K % 256 == 0;
-}
-// hsp0 != nullptr (greedy decode): h0 split into the 3-plane fragments k_lstm reads, on `s` after the
-// VWv GEMM, waiting for the heads only (the aux stream's x_g GEMM is still running: off the critical path)
-// init: the greedy decode's k_decode_init (the [T][B] key clear), launched on the aux stream beside
-// k_enc_v4 when there is one (it is needed only from step 1 on), else first on `s`
-struct DecodeInit {
-  int64_t* tok0;
-  int B;
-  uint64_t* keys;
-  int n;
-};
-static int encoder_launch(const Layout& L, const MP& p, const float* feats, int B, float* a_g, float* V, float* v_g,
-                          float* h0, float* c0, float* VWv, float* xg, aa_event_t* ev, int32_t flags,
-                          hipStream_t s, hipStream_t aux = nullptr, bf16x8* hsp0 = nullptr,
-                          const DecodeInit* init = nullptr) {
-  const int C = L.C, H = L.H, E = L.E;
-  const int64_t nch = (int64_t)B * C;
-  hipEvent_t fork = nullptr, join = nullptr, heads_done = nullptr;
-  hipStream_t sa = s;
-  if (aux && aux != s) {
-    AA_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-    AA_TRY(hipEventCreateWithFlags(&join, hipEventDisableTiming));
-    if (hsp0) AA_TRY(hipEventCreateWithFlags(&heads_done, hipEventDisableTiming));
-    AA_TRY(hipEventRecord(fork, s));
-    AA_TRY(hipStreamWaitEvent(aux, fork, 0));
-    sa = aux;
-  }
-  // the heads kernel also writes h0's bf16x3 fragments for the first step (no k_split_rows launch)
-  const bool heads_split = hsp0 && !(flags & AA_DECODE_FP32_ENCODER || C % 256) && (E + 2 * H) % 80 == 0 && C % 512 == 0;
-  // on one stream the heads launch (k_gemm3<5, 8, MODE_HEADS>) also does k_decode_init's stores: one
-  // launch fewer on the encoder phase's chain (the ids / keys are first read by step 0 / step 1)
-  const bool init_in_heads = init && sa == s && !(flags & AA_DECODE_FP32_ENCODER || C % 256) &&
-                             (E + 2 * H) % 80 == 0 && C % 512 == 0;
-  if (init && !init_in_heads) {
-    const int nblk = init->n / 256 + 1;
-    hipLaunchKernelGGL(k_decode_init, dim3(nblk < 1024 ? nblk : 1024), dim3(256), 0, sa, init->tok0, init->B,
-                       (int64_t)1, init->keys, init->n);
-  }
-  auto heads_xg = [&](hipStream_t st) {
-    const int NH = E + 2 * H;
-    if (flags & AA_DECODE_FP32_ENCODER || C % 256) {
-      const int MT = (B + 63) / 64, NTn = L.NHp / 64;
-      AA_TLAUNCH(ev, 4, k_enc_heads, dim3(MT * NTn), dim3(256), 0, st, a_g, B, C, E, H, L.NHp, p.heads_w, p.heads_b,
-                 v_g, h0, c0);
-    } else if (NH % 80 == 0 && C % 512 == 0) {
-      AA_TLAUNCH(ev, 4, (k_gemm3<5, 8, MODE_HEADS>), dim3(((B + 31) / 32) * (NH / 80)), dim3(512), 0, st,
-                 (const float*)a_g, B, C, NH, (const bf16x8*)p.heads_w4, (const float*)p.heads_b, v_g, 0, h0, c0, E, H,
-                 heads_split ? hsp0 : (bf16x8*)nullptr, init_in_heads ? init->tok0 : (int64_t*)nullptr,
-                 init_in_heads ? init->B : 0, init_in_heads ? init->keys : (uint64_t*)nullptr,
-                 init_in_heads ? init->n : 0);
-    } else {
-      AA_TLAUNCH(ev, 4, (k_gemm3<4, 4, MODE_HEADS>), dim3(((B + 31) / 32) * ((NH + 63) / 64)), dim3(256), 0, st,
-                 (const float*)a_g, B, C, NH, (const bf16x8*)p.heads_w4, (const float*)p.heads_b, v_g, 0, h0, c0, E, H,
-                 (bf16x8*)nullptr, (int64_t*)nullptr, 0, (uint64_t*)nullptr, 0);
-    }
-    if (heads_done) (void)hipEventRecord(heads_done, st);
-    if (xg && gemm3_ok(flags, E) && L.N5 % 80 == 0) {
-      AA_TLAUNCH(ev, 8, (k_gemm3<5, 4, MODE_PLAIN>), dim3(((B + 31) / 32) * (L.N5 / 80)), dim3(256), 0, st,
-                 (const float*)v_g, B, E, L.N5, (const bf16x8*)p.wvg4, (const float*)p.bias5, xg, L.N5, (float*)nullptr,
-                 (float*)nullptr, 0, 0, (bf16x8*)nullptr, (int64_t*)nullptr, 0, (uint64_t*)nullptr, 0);
-    } else if (xg) {
-      rec(ev, 8, st);
-      gemm_bias(v_g, E, B, p.wvg, E, L.N5, E, p.bias5, xg, L.N5, st);
-      rec(ev, 9, st);
-    }
-  };
-  const bool v4 = enc_v4(L, flags);
-  if (v4) {
-    // k_enc_v4 computes V and a_g in one pass over the feature map; the a_g branch (heads, x_g)
-    // then runs on aux beside the VWv GEMM.  (Trace: the fused avg-pool is a zero-length pair.)
-    const int nwg = (B * P + E4_ROWS - 1) / E4_ROWS;
-    if (H == 512)
-      AA_TLAUNCH(ev, 2, (k_enc_v4<32 / ENC4_NW, ENC4_NW>), dim3(nwg), dim3(64 * ENC4_NW), 0, s, feats, B, C,
-                 (const bf16x8*)p.enc_w4, (const float*)p.enc_a_b, V, a_g);
-    else
-      AA_TLAUNCH(ev, 2, k_enc_v4<2>, dim3(nwg), dim3(512), 0, s, feats, B, C, (const bf16x8*)p.enc_w4,
-                 (const float*)p.enc_a_b, V, a_g);
-    if (sa != s) {  // aux waits for a_g
-      hipEvent_t agr = nullptr;
-      AA_TRY(hipEventCreateWithFlags(&agr, hipEventDisableTiming));
-      AA_TRY(hipEventRecord(agr, s));
-      AA_TRY(hipStreamWaitEvent(sa, agr, 0));
-      AA_TRY(hipEventDestroy(agr));
-    }
-    heads_xg(sa);
-  } else {
-    AA_TLAUNCH(ev, 0, k_avgpool, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, sa, feats, nch, a_g);
-    heads_xg(sa);
-    if (flags & AA_DECODE_FP32_ENCODER) {
-      const int M = B * P, MT = (M + 63) / 64, NTn = H / 64;
-      AA_TLAUNCH(ev, 2, k_enc_v, dim3(MT * NTn), dim3(256), 0, s, feats, B, C, H, (const float*)p.enc_a_w,
-                 (const float*)p.enc_a_b, V);
-    } else {
-      const int M = B * P, MT = (M + EV_BM - 1) / EV_BM, NTn = H / EV_BN;
-      AA_TLAUNCH(ev, 2, k_enc_v3, dim3(MT * NTn), dim3(256), 0, s, feats, B, C, H, (const bf16x8*)p.enc_w3,
-                 (const float*)p.enc_a_b, V);
-    }
-  }
-  if (VWv && gemm3_ok(flags, H)) {
-    AA_TLAUNCH(ev, 6, (k_gemm3<4, 4, MODE_PLAIN>), dim3((B * P + 31) / 32), dim3(256), 0, s, (const float*)V, B * P, H,
-               PP, (const bf16x8*)p.wv4, (const float*)nullptr, VWv, PP, (float*)nullptr, (float*)nullptr, 0, 0,
-               (bf16x8*)nullptr, (int64_t*)nullptr, 0, (uint64_t*)nullptr, 0);
-  } else if (VWv) {
-    rec(ev, 6, s);
-    gemm_bias(V, H, B * P, p.wv, H, PP, H, nullptr, VWv, PP, s);
-    rec(ev, 7, s);
-  }
-  if (hsp0 && !heads_split) {
-    if (heads_done) AA_TRY(hipStreamWaitEvent(s, heads_done, 0));
-    hipLaunchKernelGGL(k_split_rows, dim3((unsigned)(((int64_t)B * (H / 8) + 255) / 256)), dim3(256), 0, s, h0, B, H,
-                       hsp0);
-  }
-  if (heads_done) AA_TRY(hipEventDestroy(heads_done));
-  if (join) {
-    AA_TRY(hipEventRecord(join, sa));
-    AA_TRY(hipStreamWaitEvent(s, join, 0));
-    AA_TRY(hipEventDestroy(join));
-    AA_TRY(hipEventDestroy(fork));
-  }
-  return launch_status();
-}
-
-int aa_encoder_tail(const aa_model* m, const float* feats, int32_t B, float* a_g, float* V, float* v_g, float* h0,
-                    float* c0, float* VWv, int32_t flags, aa_stream_t stream) {
-  Layout L;
-  int rc = check_model(m, &L);
-  if (rc) return rc;
-  if (B < 0) return AA_ERR_SHAPE;
-  if (B == 0) return AA_OK;
-  if (!feats || !a_g || !V || !v_g || !h0 || !c0) return AA_ERR_NULL;
-  if (!al16(feats) || !al16(a_g) || !al16(V) || !al16(VWv) || !al16(v_g)) return AA_ERR_ALIGN;
-  return encoder_launch(L, resolve(m, L), feats, B, a_g, V, v_g, h0, c0, VWv, nullptr, nullptr, flags,
-                        (hipStream_t)stream);
-}
-
-// ---- workspace carving ----------------------------------------------------------------------
-struct Carver {
-  char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t n) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off = (off + n * sizeof(T) + 255) & ~size_t(255);
-    return p;
-  }
-};
-
+// (the one-step API's workspace is not made of EncWS / RowWS: V, v_g, h and c are the caller's, and
+// it holds one split-h buffer)
 struct StepWS {
   float *xg, *s, *u, *vwv, *part;
   bf16x8* hsp;
   uint64_t* keys;
   int64_t* tok0;
 };
-// split-h fragment buffer: rows padded to 32, 3 planes of bf16
-// (rows padded to whole 64-row tiles: k_lstm reads its tile's two row blocks)
-static size_t hsp_frags(const Layout& L, int B) { return (size_t)((B + 63) / 64) * 2 * (L.H / 16) * 3 * 64; }
 static StepWS carve_step(char* base, const Layout& L, int B, size_t* bytes) {
   Carver c{base};
   StepWS w;
@@ -3006,9 +1149,10 @@ static StepWS carve_step(char* base, const Layout& L, int B, size_t* bytes) {
 }
 
 struct DecodeWS {
-  float *a_g, *V, *vwv, *vg, *xg, *h[2], *c[2], *s, *u, *unorm, *part;
+  EncWS e;
+  RowWS r;
+  float* unorm;
   uint16_t* ub;
-  bf16x8* hsp[2];
   float4* summ;
   uint64_t* keys;
   int64_t* tok0;
@@ -3016,21 +1160,10 @@ struct DecodeWS {
 static DecodeWS carve_decode(char* base, const Layout& L, int B, int T, size_t* bytes) {
   Carver c{base};
   DecodeWS w;
-  w.a_g = c.take<float>((size_t)B * L.C);
-  w.V = c.take<float>((size_t)B * P * L.H);
-  w.vwv = c.take<float>((size_t)B * P * PP);
-  w.vg = c.take<float>((size_t)B * L.E);
-  w.xg = c.take<float>((size_t)B * L.N5);
-  for (int i = 0; i < 2; ++i) {
-    w.h[i] = c.take<float>((size_t)B * L.H);
-    w.c[i] = c.take<float>((size_t)B * L.H);
-  }
-  w.s = c.take<float>((size_t)B * L.H);
-  w.u = c.take<float>((size_t)B * L.H);
+  w.e = carve_enc(c, L, B);
+  w.r = carve_rows(c, L, B);
   w.unorm = c.take<float>((size_t)2 * B);  // ||u|| then ||u - bf16(u)|| per row
-  w.part = c.take<float>((size_t)B * (L.H / 16) * PART);
   w.ub = c.take<uint16_t>((size_t)((B + 127) / 128) * 128 * L.H);  // fragment order, 128-row tiles
-  for (int i = 0; i < 2; ++i) w.hsp[i] = c.take<bf16x8>(hsp_frags(L, B));
   w.summ = c.take<float4>((size_t)B * (L.Vp / VS_TILE));
   w.keys = c.take<uint64_t>((size_t)T * B);
   w.tok0 = c.take<int64_t>((size_t)B);
@@ -3053,64 +1186,28 @@ size_t aa_decode_workspace_bytes(const aa_dims* d, int32_t B, int32_t T) {
 }
 
 
-// LSTM step (GEMM + cell in one launch), shared by the step API, the greedy loop and beam search.
-// par != nullptr: beam search (rows continue rows par[] of the previous step)
-// ra != nullptr: greedy step t >= 1 with step t-1's rescoring in the same launch (k_lstm<.., RS>); the
-// tokens come from the published keys, `tok` is not read
-static void lstm_launch(const Layout& L, const MP& p, int B, const int64_t* tok, int tok_ld, const float* xg,
-                        const bf16x8* hsp_in, const float* c_in, float* h_out, bf16x8* hsp_out, float* c_out,
-                        float* s_buf, float* part, hipStream_t s, const int* par = nullptr,
-                        const RsArgs* ra = nullptr, aa_event_t* ev = nullptr, int ei = 0, bool base = false) {
-  const int H = L.H, MT = (B + 63) / 64;
-  const RsArgs none{};
-  const int64_t* tnull = nullptr;
-  if (base) {  // the baseline model's no-sentinel step (H = 512, greedy: baseline_ok()); s_buf is not written
-    if (ra)
-      AA_TLAUNCH(ev, ei, (k_lstm<512, false, true, false>), dim3(ra->NR + MT * (512 / 16)), dim3(512), 0, s, B, L.V,
-                 tnull, 0, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part,
-                 *ra);
-    else
-      AA_TLAUNCH(ev, ei, (k_lstm<512, false, false, false>), dim3(MT * (512 / 16)), dim3(512), 0, s, B, L.V, tok,
-                 tok_ld, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);
-    return;
-  }
-  aa_for_hidden(H, [&](auto h) {
-    constexpr int H_ = h.value;
-    if (par)
-      AA_TLAUNCH(ev, ei, (k_lstm<H_, true>), dim3(MT * (H_ / 16)), dim3(512), 0, s, B, L.V, tok, tok_ld,
-                 p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);
-    else if (ra)
-      AA_TLAUNCH(ev, ei, (k_lstm<H_, false, true>), dim3(ra->NR + MT * (H_ / 16)), dim3(512), 0, s, B, L.V,
-                 tnull, 0, p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part,
-                 *ra);
-    else
-      AA_TLAUNCH(ev, ei, (k_lstm<H_, false>), dim3(MT * (H_ / 16)), dim3(512), 0, s, B, L.V, tok, tok_ld,
-                 p.table, xg, hsp_in, c_in, par, p.whh3, p.wgs, h_out, hsp_out, c_out, s_buf, part, none);
-  });
+namespace aa {
+
+// LSTM step: the object of the model's hidden size launches its k_lstm form (aa_lstm.hip)
+void lstm_launch(const Layout& L, const MP& p, const StepIO& io, hipStream_t s) {
+  aa_for_hidden(L.H, [&](auto h) { lstm_launch_h<h.value>(L, p, io, s); });
 }
 
-// Attention for one step (kdiv rows per image: beam search; k_atten5b runs an image's rows together)
-static void atten_launch(const Layout& L, const MP& p, int B, const float* V, const float* vwv, const float* h_out,
-                         float* s_buf, float* part, float* u, uint16_t* ub, float* unorm, float* alpha,
-                         int64_t alpha_ld, float* beta, int64_t beta_ld, hipStream_t s, int kdiv = 1,
-                         bf16x8* ub3 = nullptr, aa_event_t* ev = nullptr, int ei = 0, bool base = false) {
-  const int H = L.H;
-  const float* sb = s_buf;
-  const float* pt = part;
-  if (base) {  // the baseline model's row (H = 512, one row per image): s_buf and beta are not touched
-    AA_TLAUNCH(ev, ei, (k_atten5<512, false>), dim3(B), dim3(512), 0, s, B, kdiv, h_out, sb, pt, V, vwv, p.wh, alpha,
-               alpha_ld, (float*)nullptr, beta_ld, u, ub, unorm, ub3);
+// Attention for one step (io.kdiv rows per image: beam search; k_atten5b runs an image's rows together)
+void atten_launch(const Layout& L, const MP& p, const StepIO& io, hipStream_t s) {
+  const int H = L.H, B = io.B, kdiv = io.kdiv;
+  const float *h = io.h_out, *sb = io.s, *pt = io.part;
+  if (io.base) {  // the baseline model's row (H = 512, one row per image): s and beta are not touched
+    AA_TLAUNCH(io.atten_ev, io.ei, (k_atten5<512, false>), dim3(B), dim3(512), 0, s, B, kdiv, h, sb, pt, io.V, io.vwv,
+               p.wh, io.alpha, io.alpha_ld, (float*)nullptr, io.beta_ld, io.u, io.ub, io.unorm, io.ub3);
     return;
   }
-#define AA_ATTEN(HPT_)                                                                                     \
-  AA_TLAUNCH(ev, ei, k_atten<HPT_>, dim3(B), dim3(256), 0, s, B, H / 16, kdiv, h_out, sb, pt, V, vwv, p.wh, alpha, \
-             alpha_ld, beta, beta_ld, u, ub, unorm, ub3)
-#define AA_ATTEN5(H_)                                                                                      \
-  AA_TLAUNCH(ev, ei, k_atten5<H_>, dim3(B), dim3(512), 0, s, B, kdiv, h_out, sb, pt, V, vwv, p.wh, alpha, \
-             alpha_ld, beta, beta_ld, u, ub, unorm, ub3)
-#define AA_ATTEN5B(KB_)                                                                                    \
-  AA_TLAUNCH(ev, ei, (k_atten5b<512, KB_>), dim3(B / KB_), dim3(512), 0, s, h_out, sb, pt, V, vwv, p.wh, alpha, \
-             alpha_ld, beta, beta_ld, u, ub, unorm, ub3)
+#define AA_ATTEN_TAIL h, sb, pt, io.V, io.vwv, p.wh, io.alpha, io.alpha_ld, io.beta, io.beta_ld, io.u, io.ub, io.unorm, io.ub3
+#define AA_ATTEN(HPT_) \
+  AA_TLAUNCH(io.atten_ev, io.ei, k_atten<HPT_>, dim3(B), dim3(256), 0, s, B, H / 16, kdiv, AA_ATTEN_TAIL)
+#define AA_ATTEN5(H_) AA_TLAUNCH(io.atten_ev, io.ei, k_atten5<H_>, dim3(B), dim3(512), 0, s, B, kdiv, AA_ATTEN_TAIL)
+#define AA_ATTEN5B(KB_) \
+  AA_TLAUNCH(io.atten_ev, io.ei, (k_atten5b<512, KB_>), dim3(B / KB_), dim3(512), 0, s, AA_ATTEN_TAIL)
   if (H == 512 && kdiv >= 2 && kdiv <= 5 && B % kdiv == 0) {  // beam: one workgroup per image
     switch (kdiv) {
       case 2: AA_ATTEN5B(2); break;
@@ -3129,20 +1226,23 @@ static void atten_launch(const Layout& L, const MP& p, int B, const float* V, co
 #undef AA_ATTEN
 #undef AA_ATTEN5
 #undef AA_ATTEN5B
+#undef AA_ATTEN_TAIL
 }
 
-// LSTM + attention for one step (fused LSTM kernel)
-static void lstm_atten_launch(const Layout& L, const MP& p, int B, const int64_t* tok, int tok_ld,
-                              const float* V, const float* vwv, const float* xg, const bf16x8* hsp_in,
-                              const float* c_in, float* h_out, bf16x8* hsp_out, float* c_out, float* s_buf, float* part, float* u, uint16_t* ub,
-                              float* unorm, float* alpha, int64_t alpha_ld, float* beta, int64_t beta_ld,
-                              const aa_trace* tr, int t, hipStream_t s, const int* par = nullptr, int kdiv = 1,
-                              bf16x8* ub3 = nullptr, const RsArgs* ra = nullptr, bool base = false) {
-  lstm_launch(L, p, B, tok, tok_ld, xg, hsp_in, c_in, h_out, hsp_out, c_out, s_buf, part, s, par, ra,
-              tr ? tr->lstm_events : nullptr, 2 * t, base);
-  atten_launch(L, p, B, V, vwv, h_out, s_buf, part, u, ub, unorm, alpha, alpha_ld, beta, beta_ld, s, kdiv, ub3,
-               tr ? tr->atten_events : nullptr, 2 * t, base);
+// LSTM + attention for one step
+void lstm_atten_launch(const Layout& L, const MP& p, const StepIO& io, hipStream_t s) {
+  lstm_launch(L, p, io, s);
+  atten_launch(L, p, io, s);
 }
+
+void split_rows_launch(const float* h, int B, int H, bf16x8* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_split_rows, dim3((unsigned)(((int64_t)B * (H / 8) + 255) / 256)), dim3(256), 0, s, h, B, H, out);
+}
+void fill_tok_launch(int64_t* tok, int B, int64_t v, hipStream_t s) {
+  hipLaunchKernelGGL(k_fill_tok, dim3((B + 255) / 256), dim3(256), 0, s, tok, B, v);
+}
+
+}  // namespace aa
 
 // The no-sentinel kernels exist for the reference's base_lstm_hidden_size only (k_atten5<512>'s path).
 static bool baseline_ok(const Layout& L) { return L.H == 512; }
@@ -3173,17 +1273,17 @@ static int step_impl(const aa_model* m, int32_t B, const int64_t* tokens_in, con
   }
   gemm_bias(v_g, L.E, B, p.wvg, L.E, L.N5, L.E, p.bias5, w.xg, L.N5, s);
   AA_TRY(hipMemsetAsync(w.keys, 0, (size_t)B * sizeof(uint64_t), s));
-  hipLaunchKernelGGL(k_split_rows, dim3((unsigned)(((int64_t)B * (L.H / 8) + 255) / 256)), dim3(256), 0, s, h_in, B,
-                     L.H, w.hsp);
+  split_rows_launch(h_in, B, L.H, w.hsp, s);
   const int64_t* tok = tokens_in;
   if (!tok) {
-    hipLaunchKernelGGL(k_fill_tok, dim3((B + 255) / 256), dim3(256), 0, s, w.tok0, B, (int64_t)1);  // <start>
+    fill_tok_launch(w.tok0, B, 1, s);  // <start>
     tok = w.tok0;
   }
-  lstm_atten_launch(L, p, B, tok, 1, V, VWv, w.xg, w.hsp, c_in, h_out, nullptr, c_out, w.s, w.part, w.u,
-                    nullptr, nullptr, alpha, P, beta, 1, nullptr, 0, s, nullptr, 1, nullptr, nullptr, base);
-  hipLaunchKernelGGL(k_vocab, dim3(((B + 63) / 64) * (L.Vp / 64)), dim3(256), 0, s, B, L.H, L.V, L.Vp, L.V, w.u, p.mlp_w,
-                     p.mlp_b, scores, w.keys);
+  lstm_atten_launch(L, p,
+                    {.B = B, .tok = tok, .V = V, .vwv = VWv, .xg = w.xg, .hsp_in = w.hsp, .c_in = c_in, .h_out = h_out,
+                     .c_out = c_out, .s = w.s, .part = w.part, .u = w.u, .alpha = alpha, .beta = beta, .base = base},
+                    s);
+  vocab_launch(L, p, B, w.u, scores, L.V, w.keys, s);
   hipLaunchKernelGGL(k_finalize, dim3((B + 255) / 256), dim3(256), 0, s, w.keys, B, 1, tokens_out, B);
   return launch_status();
 }
@@ -3215,7 +1315,8 @@ static int decode_rows(const Layout& L, const MP& p, const DecodeWS& w, int B, i
                        float* alpha, float* beta, const aa_trace* trace, hipStream_t s) {
   const bool exact = (flags & AA_DECODE_EXACT_VOCAB) != 0;
   const bool base = (flags & AA_DECODE_BASELINE) != 0;  // no-sentinel kernels; beta is not touched
-  const int H = L.H, MT = (B + 63) / 64;
+  const int H = L.H;
+  const RowWS& r = w.r;
   const bool wide = screen_wide(L);
   // the rescoring of step t-1 rides in step t's LSTM launch (k_lstm<.., RS>); the last step's has
   // its own launch
@@ -3228,17 +1329,21 @@ static int decode_rows(const Layout& L, const MP& p, const DecodeWS& w, int B, i
     uint64_t* kt = w.keys + (size_t)t * B;
     float* alt = alpha ? alpha + (size_t)t * P : nullptr;
     float* blt = beta ? beta + t : nullptr;
-    RsArgs ra{rup((B + 1) / 2, 8), L.Vp, T, t - 1, (flags & AA_DECODE_RS_SELF) ? 0 : RS_WAIT_TICKS, w.u, w.summ,
+    RsArgs ra{rup((B + 1) / 2, 8), L.Vp, T, t - 1, (flags & AA_DECODE_RS_SELF) ? 0 : RS_WAIT_TICKS, r.u, w.summ,
               p.mlp_w, p.mlp_b, kt - B, ids};
-    lstm_launch(L, p, B, tok, tok_ld, w.xg, w.hsp[cur], w.c[cur], w.h[nxt], w.hsp[nxt], w.c[nxt], w.s, w.part, s,
-                nullptr, fused && t > 0 ? &ra : nullptr, trace ? trace->lstm_events : nullptr, 2 * t, base);
-    atten_launch(L, p, B, w.V, w.vwv, w.h[nxt], w.s, w.part, w.u, exact ? nullptr : w.ub, exact ? nullptr : w.unorm,
-                 alt, (int64_t)T * P, blt, T, s, 1, nullptr, trace ? trace->atten_events : nullptr, 2 * t, base);
+    lstm_atten_launch(L, p,
+                      {.B = B, .tok = tok, .tok_ld = tok_ld, .V = w.e.V, .vwv = w.e.vwv, .xg = r.xg,
+                       .hsp_in = r.hsp[cur], .c_in = r.c[cur], .h_out = r.h[nxt], .hsp_out = r.hsp[nxt],
+                       .c_out = r.c[nxt], .s = r.s, .part = r.part, .u = r.u, .ub = exact ? nullptr : w.ub,
+                       .unorm = exact ? nullptr : w.unorm, .alpha = alt, .alpha_ld = (int64_t)T * P, .beta = blt,
+                       .beta_ld = T, .ra = fused && t > 0 ? &ra : nullptr, .base = base,
+                       .lstm_ev = trace ? trace->lstm_events : nullptr,
+                       .atten_ev = trace ? trace->atten_events : nullptr, .ei = 2 * t},
+                      s);
     aa_event_t* sev = trace ? trace->screen_events : nullptr;
     aa_event_t* rev = trace ? trace->rescore_events : nullptr;
     if (exact) {
-      AA_TLAUNCH(sev, 2 * t, k_vocab, dim3(MT * (L.Vp / 64)), dim3(256), 0, s, B, L.H, L.V, L.Vp, L.V,
-                 (const float*)w.u, p.mlp_w, p.mlp_b, (float*)nullptr, kt);
+      vocab_launch(L, p, B, r.u, nullptr, L.V, kt, s, sev, 2 * t);
       hipLaunchKernelGGL(k_key_ids, dim3((B + 255) / 256), dim3(256), 0, s, kt, B, ids + t, T);
       continue;
     }
@@ -3264,7 +1369,7 @@ static int decode_rows(const Layout& L, const MP& p, const DecodeWS& w, int B, i
     });
     if (fused && t + 1 < T) continue;  // rescored by step t+1's k_lstm
     aa_for_hidden(H, [&](auto h) {
-      AA_TLAUNCH(rev, 2 * t, k_vrescore<h.value>, dim3(B), dim3(RS_NT), 0, s, B, L.V, L.Vp, (const float*)w.u,
+      AA_TLAUNCH(rev, 2 * t, k_vrescore<h.value>, dim3(B), dim3(RS_NT), 0, s, B, L.V, L.Vp, (const float*)r.u,
                  (const float4*)w.summ, p.mlp_w, p.mlp_b, kt, ids, T, t);
     });
   }
@@ -3293,8 +1398,8 @@ static int greedy_impl(const aa_model* m, const float* feats, int32_t B, int32_t
   // (The split default writes every key it produces; step 0's k_lstm takes <start> itself.)
   const bool clear = (flags & AA_DECODE_EXACT_VOCAB) || ((flags & AA_DECODE_SPLIT_RESCORE) == 0 && T > 1);
   const DecodeInit init{w.tok0, B, w.keys, T * B};
-  rc = encoder_launch(L, p, feats, B, w.a_g, w.V, w.vg, w.h[0], w.c[0], w.vwv, w.xg,
-                      trace ? trace->encoder_events : nullptr, flags, s, aux, w.hsp[0], clear ? &init : nullptr);
+  rc = encoder_launch(L, p, feats, B, w.e.a_g, w.e.V, w.e.vg, w.r.h[0], w.r.c[0], w.e.vwv, w.r.xg,
+                      trace ? trace->encoder_events : nullptr, flags, s, aux, w.r.hsp[0], clear ? &init : nullptr);
   if (rc) return rc;
   return decode_rows(L, p, w, B, T, flags, ids, alpha, beta, trace, s);
 }
@@ -3390,8 +1495,7 @@ int aa_vocab_logits(const aa_model* m, int32_t B, const float* u, float* scores,
   if (!u || !scores) return AA_ERR_NULL;
   if (!al16(u)) return AA_ERR_ALIGN;
   const MP p = resolve(m, L);
-  hipLaunchKernelGGL(k_vocab, dim3(((B + 63) / 64) * (L.Vp / 64)), dim3(256), 0, (hipStream_t)stream, B, L.H, L.V, L.Vp, L.V,
-                     u, p.mlp_w, p.mlp_b, scores, nullptr);
+  vocab_launch(L, p, B, u, scores, L.V, nullptr, (hipStream_t)stream);
   return launch_status();
 }
 
@@ -3420,13 +1524,3 @@ int aa_synth_uniform(float* dst, int64_t n, uint64_t key, int64_t start, double 
   return launch_status();
 }
 
-// AA_DECODE_ONLY: A/B variant builds of the greedy path only (tools/build_variant.sh; the training
-// and beam entry points are then absent and adaptive_amd._lib binds only what the library exports)
-#ifndef AA_DECODE_ONLY
-// teacher-forced training step (same translation unit: reuses the encoder kernels)
-#include "aa_train.hip"
-// beam-search decode (reuses k_lstm / k_atten / k_vocab and the encoder)
-#include "aa_beam.hip"
-// seeded temperature-sampling decode (the beam's step loop with one row per image)
-#include "aa_sample.hip"
-#endif

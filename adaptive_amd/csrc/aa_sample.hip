@@ -17,6 +17,8 @@
 //
 // Step loop: aa_beam_decode's with one row per image -- k_lstm + k_atten (lstm_atten_launch), the
 // exact fp32 logits of k_vexact, then k_sample_select (one workgroup per row, one pass over the row).
+#include "aa_internal.hpp"
+
 namespace aa {
 
 constexpr int SAMPLE_VPT = BEAM_VPT;  // V <= 256 * 64, as beam_check
@@ -113,28 +115,18 @@ __global__ __launch_bounds__(256) void k_sample_select(int V, int Vp, int T, int
 }
 
 struct SampleWS {
-  float *a_g, *V, *vwv, *vg, *xg, *h[2], *c[2], *s, *u, *part, *logits;
+  EncWS e;
+  RowWS r;
+  float* logits;
   float2* gsum;
-  bf16x8* hsp[2];
   int64_t *tok0, *tok;
 };
 static SampleWS carve_sample(char* base, const Layout& L, int B, size_t* bytes) {
   Carver c{base};
   SampleWS w;
   const size_t R = (size_t)B;
-  w.a_g = c.take<float>(R * L.C);
-  w.V = c.take<float>(R * P * L.H);
-  w.vwv = c.take<float>(R * P * PP);
-  w.vg = c.take<float>(R * L.E);
-  w.xg = c.take<float>(R * L.N5);
-  for (int i = 0; i < 2; ++i) {
-    w.h[i] = c.take<float>(R * L.H);
-    w.c[i] = c.take<float>(R * L.H);
-    w.hsp[i] = c.take<bf16x8>(hsp_frags(L, B));
-  }
-  w.s = c.take<float>(R * L.H);
-  w.u = c.take<float>(R * L.H);
-  w.part = c.take<float>(R * (L.H / 16) * PART);
+  w.e = carve_enc(c, L, R);
+  w.r = carve_rows(c, L, R);
   w.logits = c.take<float>(R * L.Vp);
   w.gsum = c.take<float2>(R * (L.Vp / 32));  // k_vexact's granule summaries (written, not read here)
   w.tok0 = c.take<int64_t>(R);
@@ -185,20 +177,22 @@ int aa_sample_decode(const aa_model* m, const float* feats, int32_t B, int32_t T
   if (workspace_bytes < need) return AA_ERR_BUFFER;
   hipStream_t s = (hipStream_t)stream;
   const MP p = resolve(m, L);
-  const int H = L.H;
-  rc = encoder_launch(L, p, feats, B, w.a_g, w.V, w.vg, w.h[0], w.c[0], w.vwv, w.xg, nullptr, flags, s);
+  const EncWS& e = w.e;
+  const RowWS& r = w.r;
+  rc = encoder_launch(L, p, feats, B, e.a_g, e.V, e.vg, r.h[0], r.c[0], e.vwv, r.xg, nullptr, flags, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_split_rows, dim3((unsigned)(((int64_t)B * (H / 8) + 255) / 256)), dim3(256), 0, s, w.h[0], B, H,
-                     w.hsp[0]);
-  hipLaunchKernelGGL(k_fill_tok, dim3((B + 255) / 256), dim3(256), 0, s, w.tok0, B, (int64_t)1);  // <start>
+  split_rows_launch(r.h[0], B, L.H, r.hsp[0], s);
+  fill_tok_launch(w.tok0, B, 1, s);  // <start>
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     // alpha / beta straight to the outputs, with the greedy decode's leading dimensions
-    lstm_atten_launch(L, p, B, t ? w.tok : w.tok0, 1, w.V, w.vwv, w.xg, w.hsp[cur], w.c[cur], w.h[nxt], w.hsp[nxt],
-                      w.c[nxt], w.s, w.part, w.u, nullptr, nullptr, alpha ? alpha + (size_t)t * P : nullptr,
-                      (int64_t)T * P, beta ? beta + t : nullptr, T, nullptr, t, s, nullptr, 1, nullptr);
-    hipLaunchKernelGGL(k_vexact, dim3(((B + VX_BM - 1) / VX_BM) * (L.Vp / VX_BN)), dim3(256), 0, s, B, H, L.V, L.Vp,
-                       (const float*)w.u, p.mlp_w, p.mlp_b, w.logits, w.gsum);
+    lstm_atten_launch(L, p,
+                      {.B = B, .tok = t ? w.tok : w.tok0, .V = e.V, .vwv = e.vwv, .xg = r.xg, .hsp_in = r.hsp[cur],
+                       .c_in = r.c[cur], .h_out = r.h[nxt], .hsp_out = r.hsp[nxt], .c_out = r.c[nxt], .s = r.s,
+                       .part = r.part, .u = r.u, .alpha = alpha ? alpha + (size_t)t * P : nullptr,
+                       .alpha_ld = (int64_t)T * P, .beta = beta ? beta + t : nullptr, .beta_ld = T, .ei = 2 * t},
+                      s);
+    vexact_launch(L, p, B, r.u, w.logits, w.gsum, s);
     AA_TLAUNCH(select_events, 2 * t, k_sample_select, dim3(B), dim3(256), 0, s, L.V, L.Vp, T, t, temperature, key, row0,
                (const float*)w.logits, w.tok, ids, logp);
   }

@@ -1,6 +1,6 @@
-// aa_train.hip — teacher-forced training step of Encoder2Decoder (forward + backward), compiled
-// into the same translation unit as aa_kernels.hip (included at its end; it reuses k_avgpool and
-// k_enc_v).  Reference: baseline_attention.py:206-230 (forward), 148-194 (Decoder), 36-62
+// aa_train.hip — teacher-forced training step of Encoder2Decoder (forward + backward), a translation
+// unit of its own (of the decode side it uses Carver and, through aa_encoder.hip's launch functions,
+// k_avgpool and k_enc_v).  Reference: baseline_attention.py:206-230 (forward), 148-194 (Decoder), 36-62
 // (AttentiveCNN tail); adaptive_attention.py:26-58 (Atten), 62-85 (Sentinel), 110-134
 // (AdaptiveBlock); train.py:101,197-219 (packed targets, CrossEntropyLoss, backward).
 //
@@ -14,6 +14,12 @@
 // order); everything else is elementwise or one-workgroup-per-row / per-image kernels with fixed
 // reduction orders, so a training step is deterministic run to run.  The cross-entropy loss is
 // the caller's (train.py computes it on the packed scores): backward starts from dL/dscores.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <vector>
+
+#include "aa_internal.hpp"
 
 namespace aa {
 
@@ -1507,6 +1513,8 @@ __global__ __launch_bounds__(256) void k_rowsum_pp(const float* __restrict__ X, 
 // ---------------------------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------------------------
+using namespace aa;
+
 constexpr size_t TR_SPLIT_FLOATS = (size_t)16 << 20;  // 64 MB split-K scratch (k_bgemm's splits of dU / dW_a)
 
 // Transposed copies of weights, several matrices per launch: dst_i[c][r] = src_i[r][c] (src row-major
@@ -1775,11 +1783,9 @@ int aa_train_forward_aux(const aa_ref_weights* w, const aa_dims* dims, const flo
     pk_rows(ga.s, w->enc_affine_a_w, C, nullptr, H, C, s.wmT, C);
     bgemm(ga, B * P, H, C, s.ftT, C, s.wmT, C, s.V, H, w->enc_affine_a_b, nullptr, 0, 1);
   } else {
-    hipLaunchKernelGGL(k_avgpool, dim3(nblk((int64_t)B * C)), dim3(256), 0, st, feats, (int64_t)B * C, s.a_g);
+    avgpool_launch(feats, (int64_t)B * C, s.a_g, st);
     f.to_aux();
-    const int M = B * P, MT = (M + 63) / 64, NTn = H / 64;
-    hipLaunchKernelGGL(k_enc_v, dim3(MT * NTn), dim3(256), 0, ga.s, feats, B, C, H, w->enc_affine_a_w,
-                       w->enc_affine_a_b, s.V);
+    enc_v_launch(feats, B, C, H, w->enc_affine_a_w, w->enc_affine_a_b, s.V, ga.s);
   }
   tgemm(ga, B * P, P, H, s.V, H, 0, w->att_affine_v_w, H, 0, s.VWv, PP);  // VWv = V W_v^T
   // the packed rows of the scores (pack_padded_sequence order), also off the chain

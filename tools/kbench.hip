@@ -3,9 +3,16 @@
 // returns the mean time per launch (hidden size 512, the harness's model).  tools/kvariant.py adds
 // copies of a kernel under study (the VARIANTS / VARIANT LAUNCH blocks) when a study needs them.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -Iinclude \
-//         tools/kbench.hip -o tools/_build/libkbench.so      (driven by tools/kbench.py)
+//         -Wl,-z,defs tools/kbench.hip -o tools/_build/libkbench.so      (driven by tools/kbench.py)
+// (the decode, encoder, beam and k_lstm units in one translation unit, so every launch function
+// aa_kernels.hip calls is defined here -- vocab_launch is aa_beam.hip's -- and the library loads on its
+// own; aa_lstm.hip without AA_LSTM_H holds every hidden size.  -Wl,-z,defs makes a missing one a link error.)
 #include "../adaptive_amd/csrc/aa_kernels.hip"
+#include "../adaptive_amd/csrc/aa_encoder.hip"
+#include "../adaptive_amd/csrc/aa_beam.hip"
+#include "../adaptive_amd/csrc/aa_lstm.hip"
 #include <stdlib.h>
+#include <string.h>
 
 using namespace aa;
 
@@ -24,11 +31,12 @@ extern "C" int kb_time(const aa_model* m, const float* feats, void* ws, int B, i
   auto launch = [&]() -> bool {
     if (!strcmp(which, "lstm")) {
       hipLaunchKernelGGL(k_lstm<512>, dim3(MT * (H / 16)), dim3(512), 0, s, B, L.V, (const int64_t*)w.tok0, 1,
-                         p.table, w.xg, w.hsp[0], w.c[0], (const int*)nullptr, p.whh3, p.wgs, w.h[1], w.hsp[1], w.c[1], w.s, w.part,
+                         p.table, w.r.xg, w.r.hsp[0], w.r.c[0], (const int*)nullptr, p.whh3, p.wgs, w.r.h[1], w.r.hsp[1], w.r.c[1], w.r.s,
+                         w.r.part,
                          RsArgs{});
     } else if (!strcmp(which, "atten5")) {
-      hipLaunchKernelGGL(k_atten5<512>, dim3(B), dim3(512), 0, s, B, 1, w.h[1], w.s, w.part, w.V, w.vwv, p.wh,
-                         (float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0, w.u, w.ub, w.unorm, (bf16x8*)nullptr);
+      hipLaunchKernelGGL(k_atten5<512>, dim3(B), dim3(512), 0, s, B, 1, w.r.h[1], w.r.s, w.r.part, w.e.V, w.e.vwv, p.wh,
+                         (float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0, w.r.u, w.ub, w.unorm, (bf16x8*)nullptr);
     } else if (!strcmp(which, "vscreen8")) {
       hipLaunchKernelGGL(k_vscreen8<512>, dim3(((B + SC2_BM - 1) / SC2_BM) * (L.Vp / SC2_BN)), dim3(SC8_NT), 0, s, B,
                          L.V, L.Vp, reinterpret_cast<const bf16x8*>(w.ub), w.unorm,
@@ -38,14 +46,14 @@ extern "C" int kb_time(const aa_model* m, const float* feats, void* ws, int B, i
                          L.V, L.Vp, reinterpret_cast<const bf16x8*>(w.ub), w.unorm,
                          reinterpret_cast<const bf16x8*>(p.mlp_wb), p.mlp_gs, p.mlp_b, w.summ);
     } else if (!strcmp(which, "vrescore")) {
-      hipLaunchKernelGGL(k_vrescore<512>, dim3(B), dim3(RS_NT), 0, s, B, L.V, L.Vp, w.u, w.summ, p.mlp_w, p.mlp_b, kt,
+      hipLaunchKernelGGL(k_vrescore<512>, dim3(B), dim3(RS_NT), 0, s, B, L.V, L.Vp, w.r.u, w.summ, p.mlp_w, p.mlp_b, kt,
                          (int64_t*)nullptr, T, t);
     } else if (!strcmp(which, "enc_v3")) {
       const int M = B * P;
-      hipLaunchKernelGGL(k_enc_v3, dim3(((M + EV_BM - 1) / EV_BM) * (H / EV_BN)), dim3(256), 0, s, feats, B, L.C, H, p.enc_w3, p.enc_a_b, w.V);
+      hipLaunchKernelGGL(k_enc_v3, dim3(((M + EV_BM - 1) / EV_BM) * (H / EV_BN)), dim3(256), 0, s, feats, B, L.C, H, p.enc_w3, p.enc_a_b, w.e.V);
     } else if (!strcmp(which, "enc_v4")) {
       hipLaunchKernelGGL((k_enc_v4<32 / ENC4_NW, ENC4_NW>), dim3((B * P + E4_ROWS - 1) / E4_ROWS), dim3(64 * ENC4_NW), 0,
-                         s, feats, B, L.C, p.enc_w4, p.enc_a_b, w.V, w.a_g);
+                         s, feats, B, L.C, p.enc_w4, p.enc_a_b, w.e.V, w.e.a_g);
     } else {
       return false;
     }

@@ -20,7 +20,7 @@ def main():
     if not os.path.exists(SO):
         os.makedirs(os.path.dirname(SO), exist_ok=True)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
-                               "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
+                               "-fPIC", "-shared", "-Wl,-z,defs", "-I" + os.path.join(ROOT, "include"),
                                os.path.join(ROOT, "tools", "kbench.hip"), "-o", SO])
     dev = torch.device("cuda", 0)
     model = Encoder2Decoder(Config()).to(dev).load_synthetic(123)

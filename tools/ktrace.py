@@ -1,7 +1,8 @@
 """Per-workgroup phase timestamps of the decode-step kernels (tools only).
 
 Build the instrumented library (s_memrealtime marks, AA_TS in the kernels) and run on the GPU box:
-    make -C adaptive_amd/csrc OUT=$PWD/tools/_build/lib_ts.so CXXFLAGS="... -DAA_TS_ENABLE"
+    make -C adaptive_amd/csrc OUT=$PWD/tools/_build/lib_ts.so OBJDIR=$PWD/tools/_build/obj_ts CXXFLAGS="... -DAA_TS_ENABLE"
+(objects of its own: the five that use AA_TS differ from the product's), then
     AA_LIB_PATH=$PWD/tools/_build/lib_ts.so python tools/ktrace.py
 Each kernel's marks come from its LAST launch in a B = 512, T = 20 decode (steady state).  Times
 are microseconds after the kernel's earliest workgroup entry; quantiles over workgroups."""

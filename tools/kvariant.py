@@ -1,4 +1,4 @@
-"""Build kernel variants for tools/kbench.hip: copy a product kernel out of aa_kernels.hip, rename it
+"""Build kernel variants for tools/kbench.hip: copy a product kernel out of its source file, rename it
 kv_<name><MODE>, apply text edits guarded by MODE, and register launch names "<name>_m<MODE>".
 usage: python tools/kvariant.py <spec.py>   (spec defines KERNEL, NAME, EDITS=[(old, new)], MODES, LAUNCH)"""
 import re
@@ -10,7 +10,10 @@ ROOT = __import__("os").path.dirname(__import__("os").path.dirname(__import__("o
 def main():
     spec = {}
     exec(open(sys.argv[1]).read(), spec)
-    src = open(f"{ROOT}/adaptive_amd/csrc/aa_kernels.hip").read()
+    # the file that holds the kernel: the units kbench.hip includes, and k_lstm's header
+    csrc = f"{ROOT}/adaptive_amd/csrc"
+    texts = [open(f"{csrc}/{f}").read() for f in ("aa_kernels.hip", "aa_lstm.hpp", "aa_encoder.hip")]
+    src = next(t for t in texts if spec["KERNEL"] in t)
     a = src.index(spec["KERNEL"])
     b = src.index("\n}\n", a) + 3
     k = src[a:b]
