@@ -92,6 +92,12 @@ class Trace(Structure):
                 ("screen_events", c_void_p), ("rescore_events", c_void_p), ("gemm_events", c_void_p)]
 
 
+class SampleOpts(Structure):
+    """aa_sample_opts: top_k (0 off), top_p (1 off), num_samples, optional kept / theta outputs."""
+    _fields_ = [("top_k", c_int32), ("top_p", c_float), ("num_samples", c_int32), ("kept", c_void_p),
+                ("theta", c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/adaptive_amd.h one to one
 SIGNATURES = {
     "aa_abi_version": (c_int, []),
@@ -139,6 +145,12 @@ SIGNATURES = {
     "aa_sample_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "aa_sample_decode": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_float, c_uint64, c_int64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p]),
+    "aa_sample_workspace_bytes_ex": (c_size_t, [POINTER(Dims), c_int32, c_int32, c_int32]),
+    "aa_sample_decode_ex": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_float, c_uint64, c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p,
+                                    POINTER(SampleOpts)]),
+    "aa_sample_select": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_uint64, c_int64,
+                                 c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "aa_synth_gumbel": (c_int, [c_void_p, c_int64, c_uint64, c_int64, c_void_p]),
     "aa_vocab_logits": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_void_p]),
     "aa_vocab_logits_at": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),

@@ -560,7 +560,8 @@ class Encoder2Decoder(nn.Module):
 
     @torch.no_grad()
     def sample(self, images: torch.Tensor, max_len: int = 20, temperature: float = 1.0, seed: int = 0,
-               row0: int = 0, select_events=None):
+               row0: int = 0, select_events=None, *, top_k: int = 0, top_p: float = 1.0, num_samples: int = 1,
+               return_kept: bool = False):
         """Seeded temperature-sampling decode (not in the reference; semantics in
         include/adaptive_amd.h and DESIGN.md) -> (ids [B,T] int64, logp [B,T], alpha [B,T,49],
         beta [B,T,1]).  Each step draws the next token from softmax(logits / temperature) by
@@ -571,7 +572,20 @@ class Encoder2Decoder(nn.Module):
         gives the same output bit for bit, and an image's draw depends only on its global row
         ``row0 + b``: rows 5..8 of a batch equal a call on those images with ``row0=5``.
         ``select_events``: address of 2 * max_len raw hipEvent handles
-        (adaptive_amd.hip_events.EventArray.ptr), a pair per step's selection launch."""
+        (adaptive_amd.hip_events.EventArray.ptr), a pair per step's selection launch.
+
+        Truncation (keyword-only): ``top_k`` keeps a token unless at least ``top_k``
+        tokens have a strictly larger logit (ties at the k-th value all stay; 0 or >= the vocabulary:
+        off); ``top_p`` in (0, 1] then keeps, of those, a token while the renormalised mass strictly
+        above it is below ``top_p`` (1: off).  The draw uses the same noise as the untruncated decode,
+        restricted to the kept set, and ``logp`` is the log-probability under the truncated,
+        renormalised distribution.  With both off the call is bit-identical to the plain one;
+        ``top_k=1`` at temperature 1 gives the greedy ids of ``sampler(exact_vocab=True)`` with logp 0.
+        ``num_samples=N`` draws N captions per image over one encoder pass: outputs have B*N rows,
+        image-major (row ``b*N + n``), equal bit for bit to
+        ``sample(images.repeat_interleave(N, 0), row0=row0*N, ...)``; ``row0`` keeps counting images.
+        ``return_kept=True`` appends ``kept [rows,T]`` int32 (the size of the kept set) and
+        ``theta [rows,T]`` fp32 (its smallest ``logit / temperature``) to the result."""
         import math
         T, tau, seed, row0 = int(max_len), float(temperature), int(seed), int(row0)
         with np.errstate(over="ignore", under="ignore"):
@@ -584,28 +598,52 @@ class Encoder2Decoder(nn.Module):
             raise ValueError(f"row0 must be >= 0, got {row0}")
         if T < 0:
             raise ValueError(f"max_len must be >= 0, got {max_len}")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 0 <= int(top_k) < (1 << 31):
+            raise ValueError(f"top_k must be an integer in [0, 2**31) (0: off), got {top_k!r}")
+        if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or int(num_samples) < 1:
+            raise ValueError(f"num_samples must be an integer >= 1, got {num_samples!r}")
+        with np.errstate(over="ignore", under="ignore"):
+            p32 = float(np.float32(top_p))  # the value the kernel compares with
+        if not (0.0 < p32 <= 1.0):  # NaN fails both
+            raise ValueError(f"top_p must be in (0, 1] (as fp32; 1: off), got {top_p!r}")
+        K, N = int(top_k), int(num_samples)
         from .synth import stream_key
         images = self._check_images(self.features(images))
         B, dev = images.size(0), images.device
-        ids = torch.empty(B, T, dtype=torch.int64, device=dev)
-        logp = torch.empty(B, T, dtype=torch.float32, device=dev)
-        alpha = torch.empty(B, T, ATT, dtype=torch.float32, device=dev)
-        beta = torch.empty(B, T, 1, dtype=torch.float32, device=dev)
+        R = B * N
+        if R > (1 << 24):
+            raise ValueError(f"num_samples: {B} images x {N} samples exceed 2**24 rows")
+        ids = torch.empty(R, T, dtype=torch.int64, device=dev)
+        logp = torch.empty(R, T, dtype=torch.float32, device=dev)
+        alpha = torch.empty(R, T, ATT, dtype=torch.float32, device=dev)
+        beta = torch.empty(R, T, 1, dtype=torch.float32, device=dev)
+        kept = torch.empty(R, T, dtype=torch.int32, device=dev) if return_kept else None
+        theta = torch.empty(R, T, dtype=torch.float32, device=dev) if return_kept else None
+        out = (ids, logp, alpha, beta) + ((kept, theta) if return_kept else ())
         if B == 0 or T == 0:
-            return ids, logp, alpha, beta
+            return out
         model = self._model_struct()
         lib = _lib.load()
-        nbytes = lib.aa_sample_workspace_bytes(self._c_dims(), B, T)
+        flags = _lib.DECODE_FP32_ENCODER if self.fp32_encoder else 0
+        plain = K == 0 and p32 == 1.0 and N == 1 and not return_kept
+        nbytes = (lib.aa_sample_workspace_bytes(self._c_dims(), B, T) if plain else
+                  lib.aa_sample_workspace_bytes_ex(self._c_dims(), B, T, N))
         if nbytes == 0:
-            raise ValueError(f"unsupported sampling configuration B={B} T={T} for {self.dims}")
+            raise ValueError(f"unsupported sampling configuration B={B} T={T} num_samples={N} for {self.dims}")
         ws = self._workspace(nbytes, dev)
         with torch.cuda.device(dev):
-            rc = lib.aa_sample_decode(model, images.data_ptr(), B, T, tau, stream_key(seed, "sample"), row0,
-                                      ids.data_ptr(), logp.data_ptr(), alpha.data_ptr(), beta.data_ptr(),
-                                      _lib.ptr(ws), ws.numel(), _lib.DECODE_FP32_ENCODER if self.fp32_encoder else 0,
-                                      _lib.stream_handle(), select_events)
+            if plain:
+                rc = lib.aa_sample_decode(model, images.data_ptr(), B, T, tau, stream_key(seed, "sample"), row0,
+                                          ids.data_ptr(), logp.data_ptr(), alpha.data_ptr(), beta.data_ptr(),
+                                          _lib.ptr(ws), ws.numel(), flags, _lib.stream_handle(), select_events)
+            else:
+                opts = _lib.SampleOpts(K, p32, N, _lib.ptr(kept), _lib.ptr(theta))
+                rc = lib.aa_sample_decode_ex(model, images.data_ptr(), B, T, tau, stream_key(seed, "sample"), row0,
+                                             ids.data_ptr(), logp.data_ptr(), alpha.data_ptr(), beta.data_ptr(),
+                                             _lib.ptr(ws), ws.numel(), flags, _lib.stream_handle(), select_events,
+                                             ctypes.byref(opts))
         _lib.check(rc, "sample_decode")
-        return ids, logp, alpha, beta
+        return out
 
     def _aux_stream(self, dev) -> torch.cuda.Stream:
         """The side stream of ``aa_greedy_decode_aux`` on ``dev``: the process's "decode-aux" role

@@ -652,6 +652,11 @@ void vexact_launch(const Layout& L, const MP& p, int R, const float* u, float* l
              p.mlp_w, p.mlp_b, logits, gsum);
 }
 
+void expand_rows_launch(const float* src, int B, int K, int n, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)(((int64_t)B * K * (n / 4) + 255) / 256)), dim3(256), 0, s, src, B, K,
+                     n, dst);
+}
+
 static int beam_check(const aa_dims* d, int B, int T, int K) {
   if (!d) return AA_ERR_NULL;
   if (aa_check_dims(d) != AA_OK) return AA_ERR_DIMS;

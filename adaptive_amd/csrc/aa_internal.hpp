@@ -338,6 +338,8 @@ void atten_launch(const Layout& L, const MP& p, const StepIO& io, hipStream_t s)
 void lstm_atten_launch(const Layout& L, const MP& p, const StepIO& io, hipStream_t s);
 void split_rows_launch(const float* h, int B, int H, bf16x8* out, hipStream_t s);      // k_split_rows
 void fill_tok_launch(int64_t* tok, int B, int64_t v, hipStream_t s);                    // k_fill_tok
+// aa_beam.hip: k_expand_rows, dst[r][:] = src[r / K][:] for the B K rows (n floats per row, a multiple of 4)
+void expand_rows_launch(const float* src, int B, int K, int n, float* dst, hipStream_t s);
 // aa_beam.hip: the exact fp32 vocab GEMMs
 // k_vocab: exact fp32 logits of R rows (scores, pitch ld; may be nullptr) and argmax keys (may be nullptr)
 void vocab_launch(const Layout& L, const MP& p, int R, const float* u, float* scores, int ld, uint64_t* keys,

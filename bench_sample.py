@@ -10,6 +10,13 @@ region by region; and, from traced passes, the median launch duration of k_sampl
 pair handed to each step's launch) and of the beam's vocab stage k_vexact.
 
     python bench_sample.py [--steps 10] [--warmup 3] [--regions 5] [--batch 512] [--T 20] [--temperature 1.0]
+                           [--top-k K] [--top-p P] [--num-samples N]
+
+With any of ``--top-k`` / ``--top-p`` / ``--num-samples`` a third region, ``sample`` with those options, is
+interleaved with the two and reported under ``"options"`` (captions/s counts the B*N drawn captions; the
+selection launch's median from its own traced passes); with ``--num-samples N > 1`` a fourth, the same
+options on ``images.repeat_interleave(N)`` -- what N draws per image cost without the shared encoder
+pass.  Without them the output is what it was.
 """
 from __future__ import annotations
 
@@ -45,6 +52,9 @@ def main():
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--T", type=int, default=20)
     ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=None, help="also time sample(top_k=K)")
+    ap.add_argument("--top-p", type=float, default=None, help="also time sample(top_p=P)")
+    ap.add_argument("--num-samples", type=int, default=None, help="also time sample(num_samples=N)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, T, K, tau = args.batch, args.T, args.steps, args.temperature
@@ -57,13 +67,24 @@ def main():
     def run_beam1():
         return model.beam_search(feats, T, 1, end_id=-1)
 
+    runs = [("sample", run_sample), ("beam1", run_beam1)]
+    opt = None
+    if args.top_k is not None or args.top_p is not None or args.num_samples is not None:
+        opt = {"top_k": args.top_k or 0, "top_p": 1.0 if args.top_p is None else args.top_p,
+               "num_samples": args.num_samples or 1}
+        runs.append(("options", lambda: model.sample(feats, T, temperature=tau, seed=0, **opt)))
+        if opt["num_samples"] > 1:
+            rep = feats.repeat_interleave(opt["num_samples"], 0)
+            runs.append(("repeat", lambda: model.sample(rep, T, temperature=tau, seed=0, top_k=opt["top_k"],
+                                                        top_p=opt["top_p"])))
     for _ in range(args.warmup):
         out = run_sample()
-        run_beam1()
+        for _, fn in runs[1:]:
+            fn()
     torch.cuda.synchronize()
-    regions = {"sample": [], "beam1": []}
-    for _ in range(args.regions):  # interleaved: both see the same clocks and the same neighbours
-        for name, fn in (("sample", run_sample), ("beam1", run_beam1)):
+    regions = {name: [] for name, _ in runs}
+    for _ in range(args.regions):  # interleaved: all see the same clocks and the same neighbours
+        for name, fn in runs:
             t0 = time.perf_counter()
             for _ in range(K):
                 fn()
@@ -82,6 +103,13 @@ def main():
         model.beam_search(feats, T, 1, end_id=-1, vocab_events=ev.ptr)
         torch.cuda.synchronize()
         vex += ev.pair_durations_ms()
+        ev.close()
+    osel = []
+    for _ in range(K if opt else 0):
+        ev = EventArray(2 * T)
+        model.sample(feats, T, temperature=tau, seed=0, select_events=ev.ptr, **opt)
+        torch.cuda.synchronize()
+        osel += ev.pair_durations_ms()
         ev.close()
     Vn = model.dims.vocab
     Vp = (Vn + 127) // 128 * 128
@@ -107,6 +135,18 @@ def main():
            "sample_over_beam1": value / beam1,
            "kernels": {"k_sample_select": stats(sel), "k_vexact(beam1)": stats(vex)}, "roofline": roofline,
            "ids_checksum": int(out[0].sum().item()), "logp_mean": float(out[1].mean().item())}
+    if opt:
+        n = opt["num_samples"]
+        o = {**opt, "value": B * n * K / el["options"], "unit": "captions/s (B * num_samples per call)",
+             "ms_per_step": 1e3 * el["options"] / K, "regions_s": regions["options"],
+             "over_sample": el["sample"] * n / el["options"], "selection_launch": stats(osel),
+             # (the same B rows in both launches only without num_samples)
+             "selection_over_k_sample_select": float(np.median(osel)) / sel_ms if n == 1 else None}
+        if "repeat" in el:
+            o["repeat_interleave"] = {"value": B * n * K / el["repeat"], "ms_per_step": 1e3 * el["repeat"] / K,
+                                      "regions_s": regions["repeat"]}
+            o["over_repeat_interleave"] = el["repeat"] / el["options"]
+        res["options"] = o
     print(json.dumps(res), flush=True)
 
 

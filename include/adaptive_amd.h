@@ -375,6 +375,64 @@ AA_API int aa_sample_decode(const aa_model* m, const float* feats, int32_t B, in
                             float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
                             aa_stream_t stream, aa_event_t* select_events);
 
+/* ---- truncated sampling (top-k / nucleus) and N draws per image --------------------------------
+ * Additions to the sampling decode; aa_sample_decode keeps its signature and behaviour (it is
+ * aa_sample_decode_ex with opts == NULL).  Semantics defined here and in tests/sample_trunc_oracle.py.
+ * Per row and step, with y[v] = x[v] / temperature (fp32, as above), m = max y, e_v = exp(y_v - m):
+ *   top-k   S_k = { v : #{ w : y_w > y_v } < top_k }: a token stays unless at least top_k tokens are
+ *           strictly better; the ties at the k-th value all stay, so |S_k| may exceed top_k.
+ *           top_k == 0 or top_k >= vocab: off (S_k is every token).
+ *   top-p   on the distribution renormalised over S_k: Z_k = sum_{S_k} e_v, G(v) = sum_{w in S_k,
+ *           y_w > y_v} e_w (the mass strictly above v), S = { v in S_k : G(v) < p Z_k }, p = top_p as
+ *           fp32, 0 < p <= 1.  p == 1 is off -- a rule, not a computation: an e_v that underflows
+ *           cannot drop a token.  The comparison is made on integers: masses floor(e_v 2^40) with
+ *           e_v = expf(y_v - m), summed in 64 bits, against ceil(p Z_k) (p taken as its exact binary
+ *           fraction).
+ *   hence   S = { v : y_v >= theta }, theta = min_{v in S} y_v: tie groups are kept or dropped
+ *           whole, and the arg-max of y is always in S (-0 and +0 are one value).
+ *   token = argmax_{v in S} (y_v + g_v), ties to the smaller v; g_v is the noise of the untruncated
+ *           decode, from the same element counter: the noise of a column does not depend on S.
+ *   logp  = y_token - (m + log sum_{v in S} e_v): the log-probability under the truncated,
+ *           renormalised distribution.
+ * With both truncations off the untruncated selection kernel runs unchanged: the same bits as
+ * aa_sample_decode.  top_k = 1 at temperature 1 gives the ids of the exact-vocab greedy decode,
+ * logp == 0 exactly and kept == 1.  Results are bit-reproducible and a row's depend on no other row.
+ * num_samples = N: N rows per image over one encoder pass (the images' V is stored and read once
+ * per image, as for the beams of aa_beam_decode).  Outputs have B N rows, image-major (row b N + n),
+ * and equal bit for bit the decode of the images repeated N times each (repeat_interleave) with
+ * row0 N in place of row0: row0 keeps counting images, so a shard of images 5..8 with row0 = 5
+ * reproduces rows 5N .. 9N - 1 of the whole batch.
+ * kept / theta (may be NULL): |S| as int32 and theta as fp32, [B N, T].
+ * Checks: as aa_sample_decode, and before the B == 0 / T == 0 return AA_ERR_SHAPE for top_k < 0,
+ * top_p not in (0, 1] (NaN included), num_samples < 1 or B N > 2^24; the counter bound is
+ * (row0 + B) N T vocab <= 2^62.  The workspace is aa_sample_workspace_bytes_ex's (encoder outputs
+ * for B images; row state, logits and tokens for B N rows; 0 for arguments the decode refuses). */
+typedef struct aa_sample_opts {
+  int32_t top_k;       /* 0: off */
+  float top_p;         /* 1: off */
+  int32_t num_samples; /* >= 1 */
+  int32_t* kept;       /* [B N, T] or NULL */
+  float* theta;        /* [B N, T] or NULL */
+} aa_sample_opts;
+AA_API size_t aa_sample_workspace_bytes_ex(const aa_dims* dims, int32_t B, int32_t T, int32_t num_samples);
+AA_API int aa_sample_decode_ex(const aa_model* m, const float* feats, int32_t B, int32_t T, float temperature,
+                               uint64_t key, int64_t row0, int64_t* ids, float* logp, float* alpha,
+                               float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
+                               aa_stream_t stream, aa_event_t* select_events, const aa_sample_opts* opts);
+
+/* One step's selection on caller-supplied logits [R, Vp] (columns V .. Vp - 1 take no part): what
+ * aa_synth_gumbel is to the noise, the selection apart from the model.  Row r is global row row0 + r
+ * of a T-step decode at step t (element counter ((row0 + r) T + t) V + v).  Writes tok[r] (int64
+ * [R]) and column t of ids [R, T] int64, logp [R, T] and, when not NULL, kept [R, T] int32 and
+ * theta [R, T].  With both truncations off it runs the untruncated selection kernel (kept = V,
+ * theta = min y).  AA_ERR_SHAPE for R < 0 or > 2^24, V outside [1, 16384], Vp < V, T < 1, t outside
+ * [0, T), a temperature that is not finite and > 0, row0 < 0, top_k < 0, top_p not in (0, 1], or
+ * (row0 + R) T V > 2^62; R == 0 returns AA_OK; then NULL logits / tok / ids / logp. */
+AA_API int aa_sample_select(const float* logits, int32_t R, int32_t V, int32_t Vp, int32_t T, int32_t t,
+                            float temperature, uint64_t key, int64_t row0, int32_t top_k, float top_p,
+                            int64_t* tok, int64_t* ids, float* logp, int32_t* kept, float* theta,
+                            aa_stream_t stream);
+
 /* The sampling decode's noise on its own (same values as adaptive_amd.synth.gumbel_f32 up to the
  * rounding of two logf): dst[i] = g of element counter start + i, i < n, as defined above. */
 AA_API int aa_synth_gumbel(float* dst, int64_t n, uint64_t key, int64_t start, aa_stream_t stream);
