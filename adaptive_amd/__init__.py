@@ -9,7 +9,8 @@ reference's model factory does.
 """
 from .synth import Dims, make_features, make_weights  # noqa: F401
 
-__all__ = ["Dims", "make_features", "make_weights", "Encoder2Decoder", "Config", "DecodePlan", "get_model"]
+__all__ = ["Dims", "make_features", "make_weights", "Encoder2Decoder", "Config", "DecodePlan", "get_model",
+           "CiderD"]
 
 
 def get_model(cf):
@@ -31,6 +32,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch/HIP
     if name in ("Encoder2Decoder", "Config", "synthetic_features", "DecodePlan"):
         from . import adaptive_attention
         return getattr(adaptive_attention, name)
+    if name == "CiderD":
+        from .cider import CiderD
+        return CiderD
     if name == "baseline_attention":
         import importlib
         return importlib.import_module(".baseline_attention", __name__)

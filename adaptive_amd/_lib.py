@@ -98,6 +98,17 @@ class SampleOpts(Structure):
                 ("theta", c_void_p)]
 
 
+CIDER_MAX_T = 64
+
+
+class CiderCorpus(Structure):
+    """aa_cider_corpus: device pointers of the CSR references and the idf table, and the scalars."""
+    _fields_ = [("img_ptr", c_void_p), ("ref_ptr", c_void_p), ("keys", c_void_p), ("counts", c_void_p),
+                ("ref_norm", c_void_p), ("ref_len", c_void_p), ("tab_keys", c_void_p), ("tab_w", c_void_p),
+                ("images", c_int32), ("refs", c_int32), ("tab_size", c_int64), ("w_unseen", c_double),
+                ("sigma", c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/adaptive_amd.h one to one
 SIGNATURES = {
     "aa_abi_version": (c_int, []),
@@ -152,6 +163,8 @@ SIGNATURES = {
     "aa_sample_select": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_uint64, c_int64,
                                  c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "aa_synth_gumbel": (c_int, [c_void_p, c_int64, c_uint64, c_int64, c_void_p]),
+    "aa_cider_score": (c_int, [POINTER(CiderCorpus), c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                               c_void_p]),
     "aa_vocab_logits": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_void_p]),
     "aa_vocab_logits_at": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "aa_cross_entropy_workspace_bytes": (c_size_t, [c_int32]),

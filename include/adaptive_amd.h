@@ -501,6 +501,68 @@ AA_API size_t aa_clip_grad_norm_workspace_bytes(const aa_grad_tensor* tensors, i
 AA_API int aa_clip_grad_norm(const aa_grad_tensor* tensors, int32_t n, float max_norm, float* total_norm,
                              void* workspace, size_t workspace_bytes, aa_stream_t stream);
 
+/* ---- CIDEr-D of token-id captions (the figure train.py selects models by; the sampling reward) ---
+ * The reference's coco/pycocoevalcap/cider/cider_scorer.py (reached from coco_eval, tools/utils.py:
+ * 234-250) on token ids in place of words; restated on the CPU by tests/cider_oracle.py.  Despite the
+ * file's name it is CIDEr-D: clipped counts and a Gaussian length penalty.
+ * A caption is the ids before the row's first end_id, or all T without one (captions.ids_to_sentences).
+ * For a caption w_0 .. w_{L-1} and the orders n = 1..4:
+ *   c(g)    = the count of the contiguous n-gram g
+ *   df(g)   = the number of corpus images with g in any of their references; M = the corpus's images
+ *   w(g)    = log M - log max(1, df(g))    (natural log, float64, computed on the host; an n-gram the
+ *             corpus never saw has w = log M = w_unseen)
+ *   vec(g)  = c(g) w(g);   norm_n = sqrt(sum_{|g| = n} vec(g)^2)
+ *   length  = the number of BIGRAMS, max(L - 1, 0): the reference adds the term frequencies where its
+ *             zero-based order index is 1, the bigram slot.  This is reproduced, not corrected: scores
+ *             are the reference's.
+ *   per reference r of the row's image and order n, in this order of operations:
+ *     val_n  = sum_{g in hyp, |g| = n} min(vec_h(g), vec_r(g)) vec_r(g)      (vec_r(g) = 0 when absent)
+ *     if norm_h,n != 0 and norm_r,n != 0:  val_n /= norm_h,n norm_r,n
+ *     val_n *= exp(-(length_h - length_r)^2 / (2 sigma^2))                   (the reference: sigma = 6)
+ *   score   = 10 mean_n(sum_r val_n) / #refs;  an empty caption scores 0.
+ * All arithmetic is float64 without contraction; the sums are wave butterflies in a fixed order, so a
+ * row's score is bit-reproducible and depends on no other row.
+ * n-gram key: key(g) = sum_{j < n} (tok_j + 1) << 16 j, uint64: exact and collision-free for tokens in
+ *   [0, 65535); the order is the number of non-zero 16-bit fields, 0 is no key.
+ * aa_cider_corpus: a host struct of device pointers, built once per corpus (adaptive_amd.cider.CiderD).
+ *   References are CSR: image i owns references img_ptr[i] .. img_ptr[i + 1] - 1, reference r the
+ *   entries ref_ptr[r] .. ref_ptr[r + 1] - 1 of keys (ascending within a reference) and counts;
+ *   ref_norm[r][n - 1] and ref_len[r] (its bigram count) are precomputed with the same w.
+ *   w(g) is an open-addressing table of tab_size slots (a power of two, load factor <= 0.5): a key sits
+ *   at slot splitmix64(key) & (tab_size - 1) or the next free one after it (linear probing, wrapping),
+ *   tab_keys 0 = empty, tab_w its weight; splitmix64 as in aa_synth_uniform.  A miss is w_unseen.
+ *   The document frequencies may come from another corpus than the references (a reward against the
+ *   training set's statistics) or from the references themselves (the reference's compute_score).
+ * aa_cider_score: scores[r] (float64 [R]) = the score of row r of ids [R, T] (int64, row pitch ids_ld)
+ *   against image image[r] of the corpus (int32 [R]; NULL: row r against image r).  One launch, no
+ *   workspace, no allocation, no synchronisation.  A token outside [0, 65535) before the row's first
+ *   end_id, or an image outside [0, images), makes that row's score NaN (as a bad target does in
+ *   aa_cross_entropy_forward); tokens after the first end_id are not looked at.  Every loop over the
+ *   corpus's data is bounded, so a malformed table gives a wrong score and never a kernel that does
+ *   not end; the CSR offsets themselves are trusted.
+ * Checks: AA_ERR_SHAPE for R < 0, T outside [0, AA_CIDER_MAX_T] or ids_ld < T; R == 0 returns AA_OK
+ *   before any pointer is looked at; then AA_ERR_NULL for a NULL corpus, AA_ERR_SHAPE for images < 1,
+ *   refs < 1, a tab_size that is not a power of two, or a sigma that is not finite and > 0; then
+ *   AA_ERR_NULL for a NULL corpus array, scores, or ids (ids may be NULL when T == 0). */
+#define AA_CIDER_MAX_T 64
+typedef struct aa_cider_corpus {
+  const int32_t* img_ptr;   /* [images + 1] */
+  const int32_t* ref_ptr;   /* [refs + 1] */
+  const uint64_t* keys;     /* [ref_ptr[refs]], ascending within a reference */
+  const int32_t* counts;    /* [ref_ptr[refs]] */
+  const double* ref_norm;   /* [refs][4] */
+  const int32_t* ref_len;   /* [refs]: bigram counts */
+  const uint64_t* tab_keys; /* [tab_size], 0 = empty */
+  const double* tab_w;      /* [tab_size] */
+  int32_t images, refs;
+  int64_t tab_size;         /* a power of two */
+  double w_unseen;          /* log(images of the document-frequency corpus) */
+  double sigma;
+} aa_cider_corpus;
+AA_API int aa_cider_score(const aa_cider_corpus* corpus, const int64_t* ids, int32_t R, int32_t T,
+                          int64_t ids_ld, int32_t end_id, const int32_t* image, double* scores,
+                          aa_stream_t stream);
+
 /* Measurement helper (bench.py's roofline block; not on the decode path): one streaming read of
  * nbytes (multiple of 16, 16-B aligned) from src by `blocks` workgroups, each writing its partial sum
  * to out[block].  Timed over a buffer resident in the 256 MiB Infinity Cache it gives the MALL-served
