@@ -32,14 +32,16 @@ ATT = 49  # attention width / spatial locations (adaptive_attention.py:16-19)
 
 
 class OracleModel:
-    """Holds fp32 CPU tensors keyed like the reference state dict."""
+    """Holds CPU tensors keyed like the reference state dict: fp32 by default; ``dtype=torch.float64``
+    runs the same program text in double (the high-precision reference of the training tests)."""
 
-    def __init__(self, state: Dict[str, np.ndarray]):
-        self.w = {k: torch.from_numpy(np.ascontiguousarray(v)).float() for k, v in state.items()}
+    def __init__(self, state: Dict[str, np.ndarray], dtype: torch.dtype = torch.float32):
+        self.dtype = dtype
+        self.w = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype) for k, v in state.items()}
         H = self.w["decoder.LSTM.weight_hh_l0"].shape[1]
         In = self.w["decoder.LSTM.weight_ih_l0"].shape[1]
         # nn.LSTM(embed*2, hidden, 1, batch_first=True)  (baseline_attention.py:140)
-        self.lstm = torch.nn.LSTM(In, H, 1, batch_first=True)
+        self.lstm = torch.nn.LSTM(In, H, 1, batch_first=True).to(dtype)
         with torch.no_grad():
             for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
                 getattr(self.lstm, n).copy_(self.w["decoder.LSTM." + n])
@@ -83,7 +85,7 @@ class OracleModel:
     def adaptive(self, x, hiddens, cells, V):
         w = self.w
         B, H = x.size(0), hiddens.size(2)
-        h0 = torch.zeros(1, B, H).transpose(0, 1)                                           # :116 init_hidden
+        h0 = torch.zeros(1, B, H, dtype=x.dtype).transpose(0, 1)                            # :116 init_hidden
         if hiddens.size(1) > 1:
             hiddens_t_1 = torch.cat((h0, hiddens[:, :-1, :]), dim=1)                        # :120
         else:
@@ -102,8 +104,8 @@ class OracleModel:
         embeddings = F.embedding(captions, w["decoder.embed.weight"])                      # :151
         x = torch.cat((embeddings, v_g.unsqueeze(1).expand_as(embeddings)), dim=2)         # :154
         H = self.lstm.hidden_size
-        hiddens = torch.zeros(x.size(0), x.size(1), H)                                      # :161-163
-        cells = torch.zeros(x.size(1), x.size(0), H)
+        hiddens = torch.zeros(x.size(0), x.size(1), H, dtype=x.dtype)                       # :161-163
+        cells = torch.zeros(x.size(1), x.size(0), H, dtype=x.dtype)
         for time_step in range(x.size(1)):                                                  # :167
             x_t = x[:, time_step, :].unsqueeze(1)
             h_t, states = self.lstm(x_t, states)                                            # :172
@@ -152,8 +154,8 @@ class TrainOracle(OracleModel):
     ``nn.LSTM`` whose parameters are those leaves.  D2 is moot here: the states
     are transposed out of place.  Returns the packed scores like ``pack_padded_sequence``."""
 
-    def __init__(self, state: Dict[str, np.ndarray]):
-        super().__init__(state)
+    def __init__(self, state: Dict[str, np.ndarray], dtype: torch.dtype = torch.float32):
+        super().__init__(state, dtype)
         for v in self.w.values():
             v.requires_grad_(True)
         self.lstm.train()
