@@ -527,7 +527,10 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
     for (int i = 0; i < GPL; ++i)
       if (gm[i] != -INFINITY) S += gv[i] * expf(gm[i] - M);
     S = wave_sum(S);
-    // K-th largest granule max (by value, then lower granule first)
+    // K-th largest granule max (by value, then lower granule first); a row with fewer than K
+    // non-empty granules (V <= 32 (K - 1)) runs out of them (best == 0) and keeps the last one found,
+    // its smallest granule max, so every non-empty granule is a candidate.  A live row has at least
+    // one (V >= 1), so kth != 0 and theta is a logit, never the NaN that key 0 decodes to.
     uint64_t prev = ~0ull, kth = 0;
     for (int j = 0; j < K; ++j) {
       uint64_t best = 0;
@@ -539,7 +542,7 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
       }
       best = wave_max_u64(best);
       prev = best;
-      kth = best;
+      if (best != 0) kth = best;
     }
     const float theta = key_value((uint32_t)(kth >> 32));
     // candidate granules (gm >= theta), compacted in granule order
@@ -588,7 +591,9 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
       } else {
         const uint64_t tk = s_top[q][j];
         const float xv = key_value((uint32_t)(tk >> 32));
-        key = argmax_key((ocum + ((xv - s_mx[q]) - s_ls[q])) + 0.0f, q * V + (int)key_token(tk));
+        // tk == 0: no j-th candidate (cannot happen with K <= V: the candidate granules hold
+        // min(K, V) columns or more); its key stays 0, which no round below selects
+        if (tk != 0) key = argmax_key((ocum + ((xv - s_mx[q]) - s_ls[q])) + 0.0f, q * V + (int)key_token(tk));
       }
     }
     for (int jj = 0; jj < K; ++jj) {

@@ -211,7 +211,7 @@ class BeamOracle(OracleModel):
         states = (h.repeat_interleave(K, 1), c.repeat_interleave(K, 1))
         nv = self.w["decoder.adaptive.mlp.weight"].shape[0]
         tok = torch.ones(B * K, 1, dtype=torch.long)                               # <start> = 1
-        cum = torch.zeros(B, K)
+        cum = torch.zeros(B, K, dtype=self.dtype)
         fin = torch.zeros(B, K, dtype=torch.bool)
         htok, hpar, hal, hbe = [], [], [], []
         base = (torch.arange(B) * K).unsqueeze(1)
@@ -247,8 +247,8 @@ class BeamOracle(OracleModel):
         T = max_len
         seqs = torch.zeros(B, K, T, dtype=torch.long)
         ids = torch.zeros(B, T, dtype=torch.long)
-        al = torch.zeros(B, T, hal[0].size(2)) if T else torch.zeros(B, 0, ATT)
-        be = torch.zeros(B, T, 1)
+        al = torch.zeros(B, T, hal[0].size(2), dtype=self.dtype) if T else torch.zeros(B, 0, ATT, dtype=self.dtype)
+        be = torch.zeros(B, T, 1, dtype=self.dtype)
         j = torch.arange(K).expand(B, K).clone()
         for t in range(T - 1, -1, -1):
             seqs[:, :, t] = htok[t].gather(1, j)
