@@ -28,6 +28,7 @@ DECODE_SCREEN4 = 4096  # vocab screen on k_vscreen2 (4 waves) instead of k_vscre
 DECODE_BASELINE = 8192  # baseline (no-sentinel) model: must match how the model was packed
 BEAM_FAST = 256
 TRAIN_BF16 = 128
+TRAIN_SENTINEL_H0 = 64  # the sentinel gate without its h_{t-1} term, as the one-token decode step
 MAX_BEAM = 8
 
 
@@ -172,6 +173,12 @@ SIGNATURES = {
                                          c_void_p, c_size_t, c_void_p]),
     "aa_cross_entropy_backward": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p, c_size_t, c_void_p, c_int64, c_void_p]),
+    "aa_policy_loss_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "aa_policy_loss_forward": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                       c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "aa_policy_loss_backward": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                        c_int32, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int64,
+                                        c_void_p]),
     "aa_adam_step": (c_int, [POINTER(AdamTensor), c_int32, c_double, c_double, c_double, c_double, c_double,
                              c_double, c_void_p]),
     "aa_clip_grad_norm_workspace_bytes": (c_size_t, [POINTER(GradTensor), c_int32]),

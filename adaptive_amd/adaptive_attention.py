@@ -28,7 +28,7 @@ raises for B > 1) is not reproduced: the sampler uses the baseline's transpose s
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -829,8 +829,93 @@ class Encoder2Decoder(nn.Module):
         if T > captions.size(1):
             raise ValueError("lengths exceed the caption width")
         caps = captions.to(device=dev, dtype=torch.int64).contiguous()
-        data = _TeacherForced.apply(self, images, caps, len_dev, N, T, *self._ref_params())
+        data = _TeacherForced.apply(self, images, caps, len_dev, N, T, self._train_flags(), *self._ref_params())
         return PackedSequence(data, batch_sizes.clone())
+
+    # ---- self-critical sequence training ---------------------------------
+    def forward_sampled(self, images, ids, num_samples: int = 1, sampler_gate: bool = False):
+        """The teacher-forced forward over sampled captions, every one at its full length ->
+        scores [T*R, V], t-major (row ``t*R + r`` is caption r at step t), differentiable in every
+        parameter and in ``images``.  ``ids`` [B*N, T] int64 are ``sample(images, num_samples=N)``'s,
+        image-major (row ``b*N + n``); the input captions are ``[<start> = 1, ids[:, :T-1]]`` and the
+        features are repeated N times per image (autograd sums their gradient back).  All lengths are T,
+        so the rows are trivially sorted and nothing is read back from the device; what follows a
+        caption's ``<end>`` is masked by ``optim.policy_gradient_loss``.  Honours ``train_bf16`` and
+        ``train_aux_stream`` as ``forward`` does.
+        ``sampler_gate=True`` computes the sentinel gate as the decoders do: the reference's ``sampler``
+        calls the decoder one token at a time, which leaves the ``h_{t-1}`` term out of the gate at
+        every step, while its teacher-forced forward (the default here) has it from step 1 on.  With it
+        the scores are those ``sample`` / ``sampler`` / ``beam_search`` drew from, to rounding, and the
+        gradient of ``decoder.adaptive.sentinel.affine_h.weight`` is an exact zero."""
+        if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or int(num_samples) < 1:
+            raise ValueError(f"num_samples must be an integer >= 1, got {num_samples!r}")
+        N = int(num_samples)
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
+            raise TypeError("ids must be an int64 tensor [B * num_samples, T]")
+        B = images.size(0) if images.dim() > 0 else 0
+        if ids.dim() != 2 or ids.size(0) != B * N or ids.size(1) < 1 or B == 0:
+            raise ValueError(f"ids must be [B * num_samples, T] = [{B * N}, T >= 1], got {tuple(ids.shape)}")
+        images = self._check_images(self.features(images))
+        dev = images.device
+        if ids.device != dev:
+            raise RuntimeError(f"ids are on {ids.device}, images on {dev}")
+        R, T = ids.shape
+        caps = torch.empty(R, T, dtype=torch.int64, device=dev)
+        caps[:, 0] = 1  # <start>
+        caps[:, 1:] = ids[:, :T - 1]
+        feats = images.repeat_interleave(N, 0) if N > 1 else images
+        lengths = (T,) * R
+        cache = self.__dict__.setdefault("_len_dev_cache", {})
+        key = (dev, lengths)
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) > 64:
+                cache.clear()
+            hit = cache[key] = (torch.tensor(lengths, dtype=torch.int32, device=dev),
+                                torch.tensor(packed_batch_sizes(lengths), dtype=torch.int64), R * T)
+        flags = self._train_flags() | (_lib.TRAIN_SENTINEL_H0 if sampler_gate else 0)
+        return _TeacherForced.apply(self, feats, caps, hit[0], R * T, T, flags, *self._ref_params())
+
+    def self_critical_loss(self, images, scorer, image_index=None, *, num_samples: int = 5, max_len: int = 20,
+                           temperature: float = 1.0, seed: int = 0, row0: int = 0):
+        """One self-critical step's loss -> ``(loss, info)``: N captions per image drawn by
+        ``sample(num_samples=N, temperature, seed, row0)``, the greedy caption of ``sampler(max_len)`` as
+        the baseline, the advantage ``scorer.score(sample) - scorer.score(greedy)`` (``scorer``: a
+        ``CiderD`` on the images' device; ``image_index`` [B] names the images' references, default image
+        b), ``forward_sampled(sampler_gate=True)`` over the draws (the distribution they were drawn
+        from) and ``optim.policy_gradient_loss`` at the same temperature and the scorer's ``end_id``.  ``loss.backward()`` fills every parameter's gradient.
+        ``info`` (``SelfCriticalInfo``) holds device tensors only and nothing here synchronises with the
+        host: ``sample_ids`` [B*N, T], ``greedy_ids`` [B, T], ``advantage`` [B*N] (float64),
+        ``logp`` [B*N, T] (the loss's, from the training forward; 0 after ``<end>``), ``sample_logp``
+        (the decode's), ``reward_sample`` [B*N], ``reward_greedy`` [B].  Truncated sampling is not
+        offered: the training forward's logits round differently from the decode's, so a kept-set
+        boundary could flip."""
+        from .optim import policy_gradient_loss
+        N = num_samples
+        sample_ids, sample_logp, _, _ = self.sample(images, max_len, temperature, seed, row0, num_samples=N)
+        greedy_ids = self.sampler(images, max_len)[0]
+        B = greedy_ids.size(0)
+        # CiderD.self_critical's expression, keeping the two rewards it is the difference of
+        idx = (torch.arange(B, device=scorer.device, dtype=torch.int32) if image_index is None
+               else scorer._index(image_index, B))
+        reward_greedy = scorer.score(greedy_ids, idx)
+        reward_sample = scorer.score(sample_ids, idx.repeat_interleave(N))
+        advantage = reward_sample - reward_greedy.repeat_interleave(N)
+        scores = self.forward_sampled(images, sample_ids, N, sampler_gate=True)
+        loss, logp = policy_gradient_loss(scores, sample_ids, advantage, scorer.end_id, temperature, return_logp=True)
+        return loss, SelfCriticalInfo(sample_ids, greedy_ids, advantage, logp, sample_logp, reward_sample,
+                                      reward_greedy)
+
+
+class SelfCriticalInfo(NamedTuple):
+    """What ``Encoder2Decoder.self_critical_loss`` computed on the way to the loss (device tensors)."""
+    sample_ids: torch.Tensor
+    greedy_ids: torch.Tensor
+    advantage: torch.Tensor
+    logp: torch.Tensor
+    sample_logp: torch.Tensor
+    reward_sample: torch.Tensor
+    reward_greedy: torch.Tensor
 
 
 def packed_batch_sizes(lengths) -> list:
@@ -856,7 +941,7 @@ class _TeacherForced(torch.autograd.Function):
     of the forward call carries the activations to the backward call."""
 
     @staticmethod
-    def forward(ctx, owner, images, caps, len_dev, N, T, *params):
+    def forward(ctx, owner, images, caps, len_dev, N, T, flags, *params):
         lib = _lib.load()
         d = owner._c_dims()
         B = images.size(0)
@@ -867,9 +952,9 @@ class _TeacherForced(torch.autograd.Function):
         with _lib.on_device(images.device):
             rc = lib.aa_train_forward_aux(w, d, images.data_ptr(), B, T, caps.data_ptr(), caps.stride(0),
                                           len_dev.data_ptr(), scores.data_ptr(), N, ws.data_ptr(), nbytes,
-                                          owner._train_flags(), _lib.stream_handle(), owner._train_aux(images.device))
+                                          flags, _lib.stream_handle(), owner._train_aux(images.device))
         _lib.check(rc, "train_forward")
-        ctx.owner, ctx.ws, ctx.N, ctx.T, ctx.flags = owner, ws, N, T, owner._train_flags()
+        ctx.owner, ctx.ws, ctx.N, ctx.T, ctx.flags = owner, ws, N, T, flags
         ctx.save_for_backward(images, caps, len_dev, *params)
         return scores
 
@@ -891,7 +976,7 @@ class _TeacherForced(torch.autograd.Function):
                                            _lib.stream_handle(), owner._train_aux(images.device))
         _lib.check(rc, "train_backward")
         ctx.ws = None
-        return (None, dfeats, None, None, None, None, *grads)
+        return (None, dfeats, None, None, None, None, None, *grads)
 
 
 def synthetic_features(B: int, device, seed: int = 0, row0: int = 0, dims: Dims = Dims()) -> torch.Tensor:

@@ -2,7 +2,8 @@
 // forward/backward (code_src/train.py:197-219): the CrossEntropyLoss on the packed scores and the
 // Adam step over every parameter.  Both are HBM-bound elementwise passes, so each is ONE launch
 // per call (Adam: every parameter tensor in one grid; cross entropy: one read of the scores
-// forward, one read + one write backward) instead of PyTorch's per-op kernel chains.
+// forward, one read + one write backward) instead of PyTorch's per-op kernel chains.  Beside the
+// cross entropy, its policy-gradient sibling for self-critical training (aa_policy_loss_*).
 //
 // Its own translation unit (linked into libadaptive_amd.so beside aa_kernels.hip).
 #include <hip/hip_runtime.h>
@@ -306,6 +307,191 @@ __global__ __launch_bounds__(CE_THREADS) void k_ce_bwd(const float* x, int64_t l
   for (; j < V; j += CE_THREADS) dr[j] = (expf(xr[j] - L) - (j == t ? 1.f : 0.f)) * scale;
 }
 
+// ---- policy-gradient (self-critical) loss over full-length sampled captions -----------------------
+// logits [T R][ldx], t-major (row t R + r = caption r at step t: the teacher-forced forward's packed
+// scores when every length is T), ids [R][ids_ld], advantage [R].  One workgroup per row, as the cross
+// entropy's.  live(r, t) = no end_id in ids[r][0 .. t-1], found by the workgroup itself.  Forward:
+// y = x / tau, logp = y[id] - logsumexp(y), term = A_r logp; k_pg_reduce: loss = -(sum term) / #live in
+// a fixed order.  Backward: dx = (exp(y - lse) - [v == id]) dloss A_r / (tau #live).  A dead row, or
+// one whose caption has A_r == 0, is never read: its term is 0 and its gradient row is written as +0.
+// An id outside [0, V) at a live position poisons the loss and that gradient row with NaN (whatever
+// A_r is), as the cross entropy's bad target does.
+__device__ __forceinline__ bool pg_live(const int64_t* __restrict__ idr, int t, int end_id) {
+  if (end_id < 0) return true;
+  int hit = 0;
+  for (int i = threadIdx.x; i < t; i += CE_THREADS) hit |= idr[i] == (int64_t)end_id;
+  return !__syncthreads_or(hit);
+}
+
+// the row's y_v = x_v / tau (x / 1 is x exactly: the division is skipped at tau == 1, same bits)
+__device__ __forceinline__ float pg_y(float x, float tau, bool unit) { return unit ? x : x / tau; }
+
+// thread 0, after the row's log-sum-exp: the row's outputs
+__device__ __forceinline__ void pg_row_out(const float* __restrict__ xr, int V, int64_t id, float A, float tau,
+                                           bool unit, float lse, int row, int64_t lp_at, float* __restrict__ lse_out,
+                                           float* __restrict__ term_out, int* __restrict__ live_out,
+                                           float* __restrict__ logp) {
+  const bool bad = id < 0 || id >= V;
+  const float lp = bad ? NAN : pg_y(xr[id], tau, unit) - lse;
+  lse_out[row] = lse;
+  term_out[row] = bad ? NAN : (A == 0.f ? 0.f : A * lp);
+  live_out[row] = 1;
+  if (logp) logp[lp_at] = lp;
+}
+
+template <bool REG>
+__global__ __launch_bounds__(CE_THREADS) void k_pg_rows(const float* __restrict__ x, int64_t ldx, int R, int T, int V,
+                                                        const int64_t* __restrict__ ids, int64_t ids_ld,
+                                                        const float* __restrict__ adv, int end_id, float tau,
+                                                        float* __restrict__ lse_out, float* __restrict__ term_out,
+                                                        int* __restrict__ live_out, float* __restrict__ logp) {
+  const int row = blockIdx.x;
+  const int t = row / R, r = row - t * R;
+  const int64_t* __restrict__ idr = ids + (int64_t)r * ids_ld;
+  const int64_t lp_at = (int64_t)r * T + t;
+  __shared__ float red[CE_THREADS / 64], red2[CE_THREADS / 64];
+  const bool live = pg_live(idr, t, end_id);  // uniform over the workgroup
+  const float A = adv[r];
+  int64_t id = 0;
+  bool skip = !live;
+  if (live) {
+    id = idr[t];
+    // nothing of the row is wanted: A_r == 0 with a valid id and no logp output
+    skip = A == 0.f && !logp && id >= 0 && id < V;
+  }
+  if (skip) {
+    if (threadIdx.x == 0) {
+      lse_out[row] = 0.f;
+      term_out[row] = 0.f;
+      live_out[row] = live ? 1 : 0;
+      if (logp) logp[lp_at] = 0.f;  // (reached by dead rows only)
+    }
+    return;
+  }
+  const float* __restrict__ xr = x + (int64_t)row * ldx;
+  const bool unit = tau == 1.f;
+  float lse;
+  if (REG) {
+    float v[CE_NPT];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < CE_NPT; ++k) {
+      const int j = threadIdx.x + k * CE_THREADS;
+      v[k] = j < V ? xr[j] : -INFINITY;
+    }
+#pragma unroll
+    for (int k = 0; k < CE_NPT; ++k) {
+      v[k] = pg_y(v[k], tau, unit);
+      m = fmaxf(m, v[k]);
+    }
+    const float M = block_reduce(m, true, red);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < CE_NPT; ++k)
+      if (threadIdx.x + k * CE_THREADS < V) s += expf(v[k] - M);
+    const float S = block_reduce(s, false, red);
+    lse = M + logf(S);
+  } else {
+    float m = -INFINITY, s = 0.f;
+    int j = threadIdx.x;
+    for (; j + 7 * CE_THREADS < V; j += 8 * CE_THREADS) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = xr[j + k * CE_THREADS];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) lse_merge(m, s, pg_y(v[k], tau, unit), 1.f);
+    }
+    for (; j < V; j += CE_THREADS) lse_merge(m, s, pg_y(xr[j], tau, unit), 1.f);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float m2 = __shfl_xor(m, off), s2 = __shfl_xor(s, off);
+      lse_merge(m, s, m2, s2);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+      red[w] = m;
+      red2[w] = s;
+    }
+    __syncthreads();
+    float M = red[0], S = red2[0];
+    for (int k = 1; k < CE_THREADS / 64; ++k) lse_merge(M, S, red[k], red2[k]);
+    lse = M + logf(S);
+  }
+  if (threadIdx.x == 0) pg_row_out(xr, V, id, A, tau, unit, lse, row, lp_at, lse_out, term_out, live_out, logp);
+}
+
+__global__ __launch_bounds__(1024) void k_pg_reduce(const float* __restrict__ term_rows,
+                                                    const int* __restrict__ live_rows, int N,
+                                                    float* __restrict__ loss, float* __restrict__ count) {
+  float s = 0.f;
+  int c = 0;
+  for (int i = threadIdx.x; i < N; i += 1024) {
+    s += term_rows[i];
+    c += live_rows[i];
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    s += __shfl_xor(s, off);
+    c += __shfl_xor(c, off);
+  }
+  __shared__ float ws[16];
+  __shared__ int wc[16];
+  if ((threadIdx.x & 63) == 0) {
+    ws[threadIdx.x >> 6] = s;
+    wc[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float S = 0.f;
+    int C = 0;
+    for (int k = 0; k < 16; ++k) {
+      S += ws[k];
+      C += wc[k];
+    }
+    count[0] = (float)C;  // >= R: step 0 of every caption is live
+    loss[0] = -S / (float)C;
+  }
+}
+
+// x and dx may alias (lddx == ldx), as in k_ce_bwd: an element is read by the thread that writes it
+__global__ __launch_bounds__(CE_THREADS) void k_pg_bwd(const float* x, int64_t ldx, int R, int T, int V,
+                                                       const int64_t* __restrict__ ids, int64_t ids_ld,
+                                                       const float* __restrict__ adv, float tau,
+                                                       const float* __restrict__ lse, const int* __restrict__ live_rows,
+                                                       const float* __restrict__ dloss, const float* __restrict__ count,
+                                                       float* dx, int64_t lddx) {
+  const int row = blockIdx.x;
+  const int t = row / R, r = row - t * R;
+  float* dr = dx + (int64_t)row * lddx;
+  const float A = adv[r];
+  int64_t id = 0;
+  bool bad = false;
+  if (live_rows[row]) {
+    id = ids[(int64_t)r * ids_ld + t];
+    bad = id < 0 || id >= V;
+  }
+  if (!live_rows[row] || (A == 0.f && !bad)) {
+    for (int j = threadIdx.x; j < V; j += CE_THREADS) dr[j] = 0.f;  // the logits are not read
+    return;
+  }
+  const float* xr = x + (int64_t)row * ldx;
+  const bool unit = tau == 1.f;
+  const float scale = bad ? NAN : (dloss[0] * A) / (tau * count[0]);
+  const float L = lse[row];
+  int j = threadIdx.x;
+  for (; j + 7 * CE_THREADS < V; j += 8 * CE_THREADS) {
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = xr[j + k * CE_THREADS];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = j + k * CE_THREADS;
+      dr[c] = (expf(pg_y(v[k], tau, unit) - L) - (c == id ? 1.f : 0.f)) * scale;
+    }
+  }
+  for (; j < V; j += CE_THREADS) dr[j] = (expf(pg_y(xr[j], tau, unit) - L) - (j == id ? 1.f : 0.f)) * scale;
+}
+
 // ---- clip_grad_norm_ (torch.nn.utils.clip_grad_norm_(params, max_norm), 2-norm; train.py:213-214) --------
 // torch: norms = _foreach_norm(grads); total = vector_norm(stack(norms)); coef = max_norm / (total +
 // 1e-6); grads *= clamp(coef, max=1).  Here: k_clip_sumsq writes one fp32 sum of squares per workgroup
@@ -534,6 +720,55 @@ int aa_cross_entropy_backward(const float* logits, int32_t N, int32_t V, int64_t
   if (dlogits == logits && lddx != ldx) return AA_ERR_SHAPE;  // in place only with the same pitch
   hipLaunchKernelGGL(k_ce_bwd, dim3(N), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, ldx, V, targets,
                      ignore_index, (const float*)workspace, dloss, count, dlogits, lddx);
+  return (int)hipGetLastError();
+}
+
+// workspace: per row its log-sum-exp, its loss term A_r logp and its live flag
+size_t aa_policy_loss_workspace_bytes(int32_t R, int32_t T) {
+  if (R <= 0 || T <= 0 || (int64_t)R * T > 0x7fffffff) return 0;
+  return (size_t)R * (size_t)T * 3 * sizeof(float);
+}
+
+static bool pg_shape_ok(int64_t ldx, int32_t R, int32_t T, int32_t V, int64_t ids_ld, float temperature) {
+  return R > 0 && T > 0 && V > 0 && ldx >= V && ids_ld >= T && isfinite(temperature) && temperature > 0.f &&
+         (int64_t)R * T <= 0x7fffffff;
+}
+
+int aa_policy_loss_forward(const float* logits, int64_t ldx, int32_t R, int32_t T, int32_t V, const int64_t* ids,
+                           int64_t ids_ld, const float* advantage, int32_t end_id, float temperature, float* loss,
+                           float* count, float* logp, void* workspace, size_t workspace_bytes, aa_stream_t stream) {
+  if (!pg_shape_ok(ldx, R, T, V, ids_ld, temperature)) return AA_ERR_SHAPE;
+  if (!logits || !ids || !advantage || !loss || !count || !workspace) return AA_ERR_NULL;  // logp may be NULL
+  if (workspace_bytes < aa_policy_loss_workspace_bytes(R, T)) return AA_ERR_BUFFER;
+  const int N = R * T;
+  float* lse = (float*)workspace;
+  float* term = lse + N;
+  int* live = (int*)(term + N);
+  hipStream_t st = (hipStream_t)stream;
+  if (V <= CE_THREADS * CE_NPT)
+    hipLaunchKernelGGL(k_pg_rows<true>, dim3(N), dim3(CE_THREADS), 0, st, logits, ldx, R, T, V, ids, ids_ld, advantage,
+                       end_id, temperature, lse, term, live, logp);
+  else
+    hipLaunchKernelGGL(k_pg_rows<false>, dim3(N), dim3(CE_THREADS), 0, st, logits, ldx, R, T, V, ids, ids_ld,
+                       advantage, end_id, temperature, lse, term, live, logp);
+  hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(1024), 0, st, term, live, N, loss, count);
+  return (int)hipGetLastError();
+}
+
+int aa_policy_loss_backward(const float* logits, int64_t ldx, int32_t R, int32_t T, int32_t V, const int64_t* ids,
+                            int64_t ids_ld, const float* advantage, int32_t end_id, float temperature,
+                            const float* dloss, const float* count, const void* workspace, size_t workspace_bytes,
+                            float* dlogits, int64_t lddx, aa_stream_t stream) {
+  (void)end_id;  // the live flags are the forward's, in the workspace
+  if (!pg_shape_ok(ldx, R, T, V, ids_ld, temperature) || lddx < V) return AA_ERR_SHAPE;
+  if (dlogits && dlogits == logits && lddx != ldx) return AA_ERR_SHAPE;  // in place only with the same pitch
+  if (!logits || !ids || !advantage || !dloss || !count || !workspace || !dlogits) return AA_ERR_NULL;
+  if (workspace_bytes < aa_policy_loss_workspace_bytes(R, T)) return AA_ERR_BUFFER;
+  const int N = R * T;
+  const float* lse = (const float*)workspace;
+  const int* live = (const int*)(lse + 2 * (size_t)N);
+  hipLaunchKernelGGL(k_pg_bwd, dim3(N), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, ldx, R, T, V, ids, ids_ld,
+                     advantage, temperature, lse, live, dloss, count, dlogits, lddx);
   return (int)hipGetLastError();
 }
 

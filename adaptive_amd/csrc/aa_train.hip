@@ -358,6 +358,7 @@ struct GemmCtx {
   float* split;
   size_t cap;  // floats
   bool bf16;   // AA_TRAIN_BF16: bf16 operands, fp32 accumulation
+  bool sent_h0 = false;  // AA_TRAIN_SENTINEL_H0: the sentinel gate without its h_{t-1} W_h term
 };
 
 // C[M,N] (+)= A W^T style helper with the common cases spelled out at the call sites.  GEMMs with
@@ -1727,7 +1728,8 @@ static void decoder_core(const GemmCtx& gc, const aa_ref_weights* w, const Train
   // sentinel (adaptive_attention.py:79-83, h_{t-1} = [0, h_0 .. h_{T-2}], :116-120)
   hipLaunchKernelGGL(k_copy_cols, dim3(nblk((int64_t)R * H)), dim3(256), 0, st, s.PRE, (int64_t)5 * H, 4 * H, s.SG,
                      (int64_t)H, R, H);
-  tgemm(gc, R - B, H, H, s.Hs, H, 0, w->sent_affine_h_w, H, 0, s.SG + (size_t)B * H, H, 1);
+  // (AA_TRAIN_SENTINEL_H0: no rows, as at T = 1 -- the gate of the one-token decode step, every step)
+  tgemm(gc, gc.sent_h0 ? 0 : R - B, H, H, s.Hs, H, 0, w->sent_affine_h_w, H, 0, s.SG + (size_t)B * H, H, 1);
   hipLaunchKernelGGL(k_tr_sent, dim3(nblk((int64_t)R * H)), dim3(256), 0, st, s.SG, s.Cs, s.S, (int64_t)R * H);
   // attention projections and the attention itself (adaptive_attention.py:26-58)
   tgemm(gc, R, P, H, s.Hs, H, 0, w->att_affine_g_w, H, 0, s.PG, PP);
@@ -1770,7 +1772,7 @@ int aa_train_forward_aux(const aa_ref_weights* w, const aa_dims* dims, const flo
   hipStream_t st = (hipStream_t)stream;
   Fork f(st, (hipStream_t)aux);
   const bool bf = (flags & AA_TRAIN_BF16) != 0;
-  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, bf};
+  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, bf, (flags & AA_TRAIN_SENTINEL_H0) != 0};
   const GemmCtx ga{f.aux, s.gsplit2, TR_SPLIT_FLOATS, bf};
   // encoder tail (baseline_attention.py:46-60), reference weight layouts: a_g and the heads on the
   // main stream (the LSTM needs them), the spatial V = relu(A W_a^T + b) and VWv on aux beside the
@@ -1864,7 +1866,7 @@ int aa_decoder_forward(const aa_ref_weights* w, const aa_dims* dims, const float
   if (workspace_bytes < need) return AA_ERR_BUFFER;
   const int H = dims->hidden, E = dims->embed, Vc = dims->vocab, R = T * B;
   hipStream_t st = (hipStream_t)stream;
-  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, (flags & AA_TRAIN_BF16) != 0};
+  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, (flags & AA_TRAIN_BF16) != 0, (flags & AA_TRAIN_SENTINEL_H0) != 0};
   hipError_t e = hipSuccess;
   if (!e) e = hipMemcpyAsync(s.V, V, sizeof(float) * (size_t)B * P * H, hipMemcpyDeviceToDevice, st);
   if (!e) e = hipMemcpyAsync(s.vg, v_g, sizeof(float) * (size_t)B * E, hipMemcpyDeviceToDevice, st);
@@ -1916,6 +1918,9 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
   const bool bf = (flags & AA_TRAIN_BF16) != 0;
   const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, bf};
   const GemmCtx ga{sa, s.gsplit2, TR_SPLIT_FLOATS, bf};
+  // AA_TRAIN_SENTINEL_H0: h_{t-1} never entered the gate, so dW_h is the K = 0 product (zeros, as at
+  // T = 1) and no gradient flows back into h_{t-1} through it
+  const int Rh = (flags & AA_TRAIN_SENTINEL_H0) ? 0 : R - B;
 #define GRAD(f) (grads->f)
   const size_t RH = (size_t)R * H;
   // Streams (Fork): main = dscores -> dU -> attention backward -> sentinel -> LSTM through time ->
@@ -2001,9 +2006,9 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
                      (int64_t)RH);
   f.to_aux();
   tgemm(ga, H, E2, R, s.dG, H, 1, s.X, E2, 1, GRAD(sent_affine_x_w), E2);               // dW_x = dG^T x
-  tgemm(ga, H, H, R - B, s.dG + (size_t)B * H, H, 1, s.Hs, H, 1, GRAD(sent_affine_h_w), H);  // dW_h = dG^T h_{t-1}
+  tgemm(ga, H, H, Rh, s.dG + (size_t)B * H, H, 1, s.Hs, H, 1, GRAD(sent_affine_h_w), H);  // dW_h = dG^T h_{t-1}
   tgemm(gc, R, E2, H, s.dG, H, 0, s.wxT, H, 0, s.dX, E2);                               // dx = dG W_x
-  tgemm(gc, R - B, H, H, s.dG + (size_t)B * H, H, 0, s.whT, H, 0, s.dH, H, 1);          // dh_{t-1} += dG W_h
+  tgemm(gc, Rh, H, H, s.dG + (size_t)B * H, H, 0, s.whT, H, 0, s.dH, H, 1);             // dh_{t-1} += dG W_h
   // LSTM backward through time (baseline_attention.py:167-178)
   AA_TRY(hipMemsetAsync(s.dh_rec, 0, (size_t)((char*)(s.dc_rec + (size_t)B * H) - (char*)s.dh_rec), st));  // adjacent
   if (gc.bf16) {

@@ -11,6 +11,11 @@ Drop-ins with the same constructor arguments, numerics (torch's op order, fp32) 
 ``Adam.state_dict()`` has torch's keys (``step`` as a CPU float32 tensor, ``exp_avg``,
 ``exp_avg_sq``), so a checkpoint moves between the two optimizers.  There is no CPU fallback: CPU
 tensors raise ``RuntimeError``.
+
+Not in the reference: ``policy_gradient_loss`` / ``PolicyGradientLoss``, the self-critical loss over
+sampled captions (``aa_policy_loss_*``; ``Encoder2Decoder.self_critical_loss`` puts the step together).
+``Adam.step()`` advances the version counter of every parameter it updates, so the model's decoders
+see the new weights.
 """
 from __future__ import annotations
 
@@ -24,6 +29,12 @@ def _require_hip(t: torch.Tensor, what: str) -> None:
         raise RuntimeError(f"adaptive_amd.optim: {what} must be a GPU tensor (the HIP kernels have no CPU path)")
     if t.dtype != torch.float32:
         raise TypeError(f"adaptive_amd.optim: {what} must be float32, got {t.dtype}")
+
+
+def _f32(x: float) -> float:
+    """``x`` rounded to fp32, the value a kernel taking a ``float`` sees."""
+    import ctypes
+    return ctypes.c_float(x).value
 
 
 class Adam(torch.optim.Optimizer):
@@ -98,6 +109,10 @@ class Adam(torch.optim.Optimizer):
                     rc = lib.aa_adam_step(arr, n, step, group["lr"], beta1, beta2, group["eps"],
                                           group["weight_decay"], _lib.stream_handle())
                 _lib.check(rc, "adam_step")
+            # the kernel wrote the parameters through raw pointers: no torch operation saw it, so their
+            # version counters are advanced here (host-side, no launch) -- Encoder2Decoder repacks its
+            # decode weights when a parameter's (data_ptr, _version) changes
+            torch.autograd.graph.increment_version(live)
         return loss
 
     def _plan(self, live, ident):
@@ -260,4 +275,103 @@ class CrossEntropyLoss(torch.nn.Module):
         return cross_entropy(input, target, self.ignore_index)
 
 
-__all__ = ["Adam", "CrossEntropyLoss", "clip_grad_norm_", "cross_entropy"]
+class _PolicyLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, ids, adv, end_id, tau, want_logp):
+        lib = _lib.load()
+        R, T = ids.shape
+        V = scores.size(1)
+        x = scores if scores.stride(1) == 1 else scores.contiguous()
+        dev = x.device
+        ws = torch.empty(lib.aa_policy_loss_workspace_bytes(R, T), dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.float32, device=dev)
+        logp = torch.empty(R, T, dtype=torch.float32, device=dev) if want_logp else None
+        with _lib.on_device(dev):
+            rc = lib.aa_policy_loss_forward(x.data_ptr(), x.stride(0), R, T, V, ids.data_ptr(), ids.stride(0),
+                                            adv.data_ptr(), end_id, tau, loss.data_ptr(), count.data_ptr(),
+                                            _lib.ptr(logp), ws.data_ptr(), ws.numel(), _lib.stream_handle())
+        _lib.check(rc, "policy_loss_forward")
+        ctx.save_for_backward(x, ids, adv, ws, count)
+        ctx.end_id, ctx.tau = end_id, tau
+        if logp is None:
+            return loss
+        ctx.mark_non_differentiable(logp)
+        return loss, logp
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        lib = _lib.load()
+        x, ids, adv, ws, count = ctx.saved_tensors
+        R, T = ids.shape
+        V = x.size(1)
+        dloss = dloss.contiguous().float()
+        dx = torch.empty(R * T, V, dtype=torch.float32, device=x.device)
+        with _lib.on_device(x.device):
+            rc = lib.aa_policy_loss_backward(x.data_ptr(), x.stride(0), R, T, V, ids.data_ptr(), ids.stride(0),
+                                             adv.data_ptr(), ctx.end_id, ctx.tau, dloss.data_ptr(), count.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), dx.data_ptr(), dx.stride(0),
+                                             _lib.stream_handle())
+        _lib.check(rc, "policy_loss_backward")
+        return dx, None, None, None, None, None
+
+
+def policy_gradient_loss(scores: torch.Tensor, ids: torch.Tensor, advantage: torch.Tensor, end_id: int = 2,
+                         temperature: float = 1.0, return_logp: bool = False):
+    """The self-critical (REINFORCE with a baseline) loss of R sampled captions trained at the full
+    length T (aa_policy_loss_*): ``scores`` [T*R, V] fp32 on the GPU, t-major (row ``t*R + r``: what
+    ``Encoder2Decoder.forward_sampled`` returns; a row pitch is read in place), ``ids`` [R, T] int64 the
+    sampled tokens, ``advantage`` [R] float32 or float64 (``CiderD.self_critical``'s; converted once).
+    A position is live until the caption's first ``end_id`` inclusive (``end_id < 0``: all are);
+    ``logp`` is the token's log-probability under ``softmax(scores / temperature)`` and the loss
+    ``-(sum over live positions of advantage[r] * logp[r, t]) / #live``, the token mean (the scale of the
+    teacher-forced stage's 'mean' cross entropy).  Differentiable in ``scores`` only; the gradient rows
+    of dead positions and of captions with advantage 0 are exact zeros, written without reading the
+    scores.  An id outside [0, V) at a live position makes the loss NaN.  ``return_logp=True``
+    returns ``(loss, logp [R, T])`` with 0 at dead positions."""
+    import math
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32:
+        raise TypeError("adaptive_amd.optim.policy_gradient_loss: scores must be a float32 tensor")
+    if scores.dim() != 2:
+        raise ValueError(f"adaptive_amd.optim.policy_gradient_loss: scores must be [T*R, V], got {tuple(scores.shape)}")
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2:
+        raise ValueError("adaptive_amd.optim.policy_gradient_loss: ids must be an int64 tensor [R, T]")
+    if ids.dtype != torch.int64:
+        raise TypeError(f"adaptive_amd.optim.policy_gradient_loss: ids must be int64, got {ids.dtype}")
+    R, T = ids.shape
+    if R == 0 or T == 0 or scores.size(0) != R * T or scores.size(1) == 0:
+        raise ValueError(f"adaptive_amd.optim.policy_gradient_loss: scores {tuple(scores.shape)} are not [T*R, V] "
+                         f"for ids {tuple(ids.shape)} (R, T >= 1)")
+    if not isinstance(advantage, torch.Tensor) or tuple(advantage.shape) != (R,):
+        raise ValueError(f"adaptive_amd.optim.policy_gradient_loss: advantage must have shape ({R},)")
+    if advantage.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"adaptive_amd.optim.policy_gradient_loss: advantage must be float32 or float64, "
+                        f"got {advantage.dtype}")
+    tau = float(temperature)
+    if not (math.isfinite(tau) and tau > 0.0 and math.isfinite(_f32(tau)) and _f32(tau) > 0.0):
+        raise ValueError(f"temperature must be finite and > 0 (as fp32), got {temperature}")
+    for t, what in ((scores, "scores"), (ids, "ids"), (advantage, "advantage")):
+        if not t.is_cuda:
+            raise RuntimeError(f"adaptive_amd.optim: {what} must be a GPU tensor (the HIP kernels have no CPU path)")
+        if t.device != scores.device:
+            raise RuntimeError(f"adaptive_amd.optim.policy_gradient_loss: {what} is on {t.device}, scores on "
+                               f"{scores.device}")
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    adv = advantage.detach().to(torch.float32).contiguous()
+    return _PolicyLoss.apply(scores, ids, adv, int(end_id), tau, bool(return_logp))
+
+
+class PolicyGradientLoss(torch.nn.Module):
+    """``policy_gradient_loss`` as a module: ``crit(scores, ids, advantage)`` -> the loss."""
+
+    def __init__(self, end_id: int = 2, temperature: float = 1.0):
+        super().__init__()
+        self.end_id, self.temperature = int(end_id), float(temperature)
+
+    def forward(self, scores, ids, advantage):
+        return policy_gradient_loss(scores, ids, advantage, self.end_id, self.temperature)
+
+
+__all__ = ["Adam", "CrossEntropyLoss", "PolicyGradientLoss", "clip_grad_norm_", "cross_entropy",
+           "policy_gradient_loss"]

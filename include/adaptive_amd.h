@@ -275,6 +275,12 @@ AA_API size_t aa_train_workspace_bytes(const aa_dims* dims, int32_t B, int32_t T
                                (operands rounded to bf16, fp32 accumulation; BASELINE config 5's
                                "bf16 compute / fp32 master"); elementwise work and the encoder V GEMM
                                stay fp32.  0 = fp32 GEMMs (fp32 MFMA).  Pass the same flags to both. */
+#define AA_TRAIN_SENTINEL_H0 64 /* the sentinel gate sigma(W_x x_t) without its h_{t-1} W_h term at every
+                               step, as the one-token decode step computes it (the reference's sampler
+                               calls Decoder.forward per token, which starts h_{t-1} from zeros each
+                               time): the forward then reproduces the distribution aa_sample_decode /
+                               aa_greedy_decode draw from; the gradient of sent_affine_h_w is written as
+                               zeros.  Also accepted by aa_decoder_forward.  Pass the same flags to both. */
 AA_API int aa_train_forward(const aa_ref_weights* w, const aa_dims* dims, const float* feats, int32_t B,
                             int32_t T, const int64_t* tokens, int32_t tok_ld, const int32_t* lengths,
                             float* scores, int32_t N, void* workspace, size_t workspace_bytes,
@@ -469,6 +475,37 @@ AA_API int aa_cross_entropy_backward(const float* logits, int32_t N, int32_t V, 
                                      const int64_t* targets, int64_t ignore_index, const float* dloss,
                                      const float* count, const void* workspace, size_t workspace_bytes,
                                      float* dlogits, int64_t lddx, aa_stream_t stream);
+
+/* ---- the policy-gradient (self-critical) loss over sampled captions trained at the full length T ----
+ * logits [T R][ldx] fp32, t-major: row t R + r is caption r at step t (the packed scores of
+ * aa_train_forward when every length is T); ids [R][ids_ld] int64 the sampled tokens; advantage [R].
+ *   live(r, t) = no end_id among ids[r][0 .. t-1] (the <end> token itself is trained; end_id < 0: every
+ *                position is live); each workgroup finds it from the ids, no extra launch
+ *   y          = x / temperature (fp32 division, as aa_sample_decode's)
+ *   logp(r, t) = y[id] - (m + log sum_v exp(y_v - m)), m = max_v y_v; 0 at a dead position
+ *   count      = #live;   loss = -(sum_live advantage[r] logp(r, t)) / count     (the token mean)
+ *   dlogits(r, t, v) = dloss[0] advantage[r] (exp(y_v - lse) - [v == id]) / (temperature count)
+ * A dead row, and a row of a caption with advantage[r] == 0, is not read: its loss term is 0 and its
+ * row of dlogits is written as +0 (the forward still reads an advantage-0 row when logp is wanted).
+ * An id outside [0, V) at a live position makes the loss NaN and that row of dlogits NaN, whatever the
+ * advantage; ids at dead positions are only compared with end_id.  A non-finite advantage propagates.
+ * Fixed-order reductions: bit-reproducible.  logp [R][T] may be NULL.  The forward's workspace
+ * (aa_policy_loss_workspace_bytes(R, T); 0 for a refused shape) carries the per-row log-sum-exp and
+ * live flags to the backward, which takes the same inputs; dlogits may alias logits only if lddx == ldx.
+ * Checks, in this order: AA_ERR_SHAPE for R <= 0, T <= 0, V <= 0, ldx < V, lddx < V, ids_ld < T, a
+ * temperature that is not finite and > 0, R T > 2^31 - 1, or in place with unequal pitches; AA_ERR_NULL;
+ * AA_ERR_BUFFER for a workspace smaller than aa_policy_loss_workspace_bytes(R, T). */
+AA_API size_t aa_policy_loss_workspace_bytes(int32_t R, int32_t T);
+AA_API int aa_policy_loss_forward(const float* logits, int64_t ldx, int32_t R, int32_t T, int32_t V,
+                                  const int64_t* ids, int64_t ids_ld, const float* advantage,
+                                  int32_t end_id, float temperature, float* loss, float* count,
+                                  float* logp, void* workspace, size_t workspace_bytes,
+                                  aa_stream_t stream);
+AA_API int aa_policy_loss_backward(const float* logits, int64_t ldx, int32_t R, int32_t T, int32_t V,
+                                   const int64_t* ids, int64_t ids_ld, const float* advantage,
+                                   int32_t end_id, float temperature, const float* dloss,
+                                   const float* count, const void* workspace, size_t workspace_bytes,
+                                   float* dlogits, int64_t lddx, aa_stream_t stream);
 
 /* aa_adam_step: one torch.optim.Adam step (model_factory.py:71: Adam(params, lr, betas, weight_decay); amsgrad=False,
  * maximize=False, L2 weight_decay added to the gradient) over n fp32 tensors, every tensor in one
