@@ -795,6 +795,23 @@ class Encoder2Decoder(nn.Module):
         _lib.check(rc, "vocab_logits")
         return out
 
+    def _lengths_on_device(self, dev, lengths):
+        """``(lengths on dev as int32, PackedSequence batch sizes, sum(lengths))`` of a tuple of lengths,
+        validated once per distinct (device, lengths) and cached: a fresh ``torch.tensor(..., device=dev)``
+        is a pageable host->device copy, which HIP may stage synchronously (the host then waits before
+        it can queue the rest of the step), and the batch sizes are an O(B T) Python loop, ~0.1 ms of
+        host time per step at B = 128."""
+        cache = self.__dict__.setdefault("_len_dev_cache", {})
+        key = (dev, lengths)
+        hit = cache.get(key)
+        if hit is None:
+            bs = packed_batch_sizes(lengths)
+            if len(cache) > 64:
+                cache.clear()
+            hit = cache[key] = (torch.tensor(lengths, dtype=torch.int32, device=dev),
+                                torch.tensor(bs, dtype=torch.int64), sum(lengths))
+        return hit
+
     # ---- Encoder2Decoder.forward (baseline_attention.py:206-230): teacher-forced training ------
     def forward(self, images, captions, lengths):
         """Teacher-forced forward -> ``PackedSequence`` of the scores, exactly as the reference's
@@ -811,20 +828,7 @@ class Encoder2Decoder(nn.Module):
         if captions.dim() != 2 or captions.size(0) != B or len(lengths) != B:
             raise ValueError("captions must be [B, L] and lengths a list of B ints")
         dev = images.device
-        # per distinct lengths list, validated once and cached: the lengths on the device (a fresh
-        # torch.tensor(..., device=dev) is a pageable host->device copy, which HIP may stage
-        # synchronously: the host then waits before it can queue the rest of the step) and the
-        # PackedSequence batch sizes (an O(B T) Python loop, ~0.1 ms of host time per step at B = 128)
-        cache = self.__dict__.setdefault("_len_dev_cache", {})
-        key = (dev, lengths)
-        hit = cache.get(key)
-        if hit is None:
-            bs = packed_batch_sizes(lengths)
-            if len(cache) > 64:
-                cache.clear()
-            hit = cache[key] = (torch.tensor(lengths, dtype=torch.int32, device=dev),
-                                torch.tensor(bs, dtype=torch.int64), sum(lengths))
-        len_dev, batch_sizes, N = hit
+        len_dev, batch_sizes, N = self._lengths_on_device(dev, lengths)
         T = lengths[0]
         if T > captions.size(1):
             raise ValueError("lengths exceed the caption width")
@@ -864,17 +868,9 @@ class Encoder2Decoder(nn.Module):
         caps[:, 0] = 1  # <start>
         caps[:, 1:] = ids[:, :T - 1]
         feats = images.repeat_interleave(N, 0) if N > 1 else images
-        lengths = (T,) * R
-        cache = self.__dict__.setdefault("_len_dev_cache", {})
-        key = (dev, lengths)
-        hit = cache.get(key)
-        if hit is None:
-            if len(cache) > 64:
-                cache.clear()
-            hit = cache[key] = (torch.tensor(lengths, dtype=torch.int32, device=dev),
-                                torch.tensor(packed_batch_sizes(lengths), dtype=torch.int64), R * T)
+        len_dev = self._lengths_on_device(dev, (T,) * R)[0]
         flags = self._train_flags() | (_lib.TRAIN_SENTINEL_H0 if sampler_gate else 0)
-        return _TeacherForced.apply(self, feats, caps, hit[0], R * T, T, flags, *self._ref_params())
+        return _TeacherForced.apply(self, feats, caps, len_dev, R * T, T, flags, *self._ref_params())
 
     def self_critical_loss(self, images, scorer, image_index=None, *, num_samples: int = 5, max_len: int = 20,
                            temperature: float = 1.0, seed: int = 0, row0: int = 0):

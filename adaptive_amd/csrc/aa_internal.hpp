@@ -9,6 +9,7 @@
 //   aa_lstm.hip       k_lstm (aa_lstm.hpp), one object per hidden size
 //   aa_kernels.hip    attention, vocab screen / rescoring, the step and greedy C ABI
 //   aa_beam.hip       beam search and the exact fp32 vocab GEMMs (k_vocab, k_vexact)
+//   aa_tgemm.hip      the training step's GEMM engine (aa_tgemm.hpp)
 //   aa_sample.hip, aa_train.hip, aa_optim.hip
 #pragma once
 #include <hip/hip_runtime.h>

@@ -9,752 +9,20 @@
 // size of t; lengths sorted descending) are a monotone subset of the rows.
 //
 // Arithmetic: fp32 throughout (with AA_TRAIN_BF16 the GEMMs take bf16 operands, fp32 accumulation).
-// GEMMs run on the generic MFMA tile kernel k_tgemm below
-// (operands in any of the layouts the backward pass needs, bounds-checked, fixed accumulation
-// order); everything else is elementwise or one-workgroup-per-row / per-image kernels with fixed
-// reduction orders, so a training step is deterministic run to run.  The cross-entropy loss is
-// the caller's (train.py computes it on the packed scores): backward starts from dL/dscores.
-#include <stdio.h>
-#include <stdlib.h>
+// GEMMs run on the generic engine of aa_tgemm.hip (k_tgemm: operands in any of the layouts the
+// backward pass needs, bounds-checked, fixed accumulation order); everything else is elementwise
+// or one-workgroup-per-row / per-image kernels with fixed reduction orders, so a training step is
+// deterministic run to run.  The cross-entropy loss is the caller's (train.py computes it on the
+// packed scores): backward starts from dL/dscores.
+#include <assert.h>
 
+#include <initializer_list>
+#include <utility>
 #include <vector>
 
-#include "aa_internal.hpp"
+#include "aa_tgemm.hpp"
 
 namespace aa {
-
-// ---------------------------------------------------------------------------------------------
-// generic GEMM: C[M, N] (+)= act(sum_k A(m, k) W(n, k) + bias[n] + bias2[n])
-//   A(m, k) = at ? A[k lda + m] : A[row(m) lda + k]        row(m) = arow ? arow[m] : m
-//   W(n, k) = wm == 0 : W[n ldw + k]
-//             wm == 1 : W[k ldw + n]
-//             wm == 2 : NCHW feature map [B][C][49] read as the [B*49, C] row matrix transposed:
-//                       W(n = c, k = b*49 + p) = W[b*ldw*49 + c*49 + p]   (ldw = C)
-//   C row m -> crow ? crow[m] : m
-// 64x64 tiles, 256 threads (2 x 2 waves of 32x32), K steps of TStep::KS through double-buffered LDS
-// (fp32 MFMA: lanes 0-31 take k = s, lanes 32-63 k = KS/2 + s of each step).
-// ---------------------------------------------------------------------------------------------
-struct TG {
-  int M, N, K;
-  const float* A;
-  int64_t lda;
-  const int* arow;
-  int at;
-  const float* W;
-  int64_t ldw;
-  int wm;
-  float* C;
-  int64_t ldc;
-  const int* crow;
-  const float* bias;
-  const float* bias2;
-  int accumulate;
-  int act;      // 0 none, 1 relu, 2 tanh
-  int splits;   // split-K: > 1 -> raw partial tiles to part[split][M][N], reduced by k_tgemm_reduce
-  int kper;     // K per split (multiple of the K step)
-  float* part;
-};
-
-// K step of the training GEMM: 64 with bf16 operands (two 32-wide halves per thread, so a
-// latency-bound GEMM -- the per-step recurrent ones, K = 128 per split -- pays half the global round
-// trips), 32 with fp32 operands (a 64-deep fp32 tile pair would need 70 KB of LDS and halve the
-// occupancy of the large GEMMs: measured slower).  Tiles [64 rows][pitch]: fp32 pitch KS + 4 floats,
-// bf16 KS + 8 bf16 (conflict-free 16-B fragment reads either way).
-template <bool BF>
-struct TStep {
-  static constexpr int KS = BF ? 64 : 32, HH = KS / 32, LDK = KS + 4, LDB = KS + 8;
-  static constexpr int TILE_F = BF ? 64 * LDB / 2 : 64 * LDK;  // one operand tile, in floats
-};
-
-// value i of a split GEMM: its S partials summed in split order from 0 (+ 0, as the reduce adds absent
-// biases), or src itself when it was not split.  Up to SK_MAX partials are loaded together before the
-// ordered sum (a loop over a runtime count waits for each load in turn).
-constexpr int SK_MAX = 16;
-__device__ __forceinline__ float sk_sum(const float* __restrict__ src, int S, int64_t MN, int64_t i) {
-  if (S == 1) return src[i];
-  float x[SK_MAX];
-#pragma unroll
-  for (int sp = 0; sp < SK_MAX; ++sp) x[sp] = sp < S ? src[sp * MN + i] : 0.f;
-  float v = 0.f;
-#pragma unroll
-  for (int sp = 0; sp < SK_MAX; ++sp)
-    if (sp < S) v += x[sp];
-  for (int sp = SK_MAX; sp < S; ++sp) v += src[sp * MN + i];
-  return v + 0.f;
-}
-
-// BF: operands rounded to bf16 (RNE) as they are staged in LDS, products on
-// v_mfma_f32_32x32x16_bf16 with fp32 accumulation (BASELINE config 5: bf16 compute, fp32 master
-// weights); same tiles, loads and epilogue as the fp32 engine.
-template <bool BF>
-__global__ __launch_bounds__(256) void k_tgemm(TG g) {
-  constexpr int TBK = TStep<BF>::KS, HH = TStep<BF>::HH, TLDK = TStep<BF>::LDK, TLDB = TStep<BF>::LDB;
-  __shared__ __attribute__((aligned(16))) float lds[2][2][TStep<BF>::TILE_F];
-  const int tilesN = (g.N + 63) / 64;
-  const int split = blockIdx.x % g.splits, tile = blockIdx.x / g.splits;
-  const int mt = tile / tilesN, nt = tile % tilesN;
-  const int kbeg = split * g.kper, kend = g.splits > 1 ? (kbeg + g.kper < g.K ? kbeg + g.kper : g.K) : g.K;
-  const int m0 = mt * 64, n0 = nt * 64;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wmv = wave >> 1, wnv = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  float ra[HH][8], rw[HH][8];  // [32-wide k half][8 consecutive elements]
-  // operands are read 8 consecutive elements per thread along their contiguous dimension, as two
-  // 16-B loads when the 8 are in bounds and aligned, else element by element with zero fill
-  const bool a4 = ((g.lda & 3) == 0) && ((((uintptr_t)g.A) & 15) == 0);
-  const bool w4 = ((g.ldw & 3) == 0) && ((((uintptr_t)g.W) & 15) == 0) && g.wm != 2;
-  auto load8 = [&](float (&r)[8], const float* base) {
-    const float4 x = *reinterpret_cast<const float4*>(base), y = *reinterpret_cast<const float4*>(base + 4);
-    r[0] = x.x; r[1] = x.y; r[2] = x.z; r[3] = x.w; r[4] = y.x; r[5] = y.y; r[6] = y.z; r[7] = y.w;
-  };
-  auto gload = [&](int k0, float (&ra)[HH][8], float (&rw)[HH][8]) {
-#pragma unroll
-    for (int hh = 0; hh < HH; ++hh) {
-      const int kh = k0 + 32 * hh;
-      if (!g.at) {  // 4 threads per row, 8 consecutive k each
-        const int r = t >> 2, kq = (t & 3) * 8, m = m0 + r;
-        const int64_t base = (int64_t)(m < g.M ? (g.arow ? g.arow[m] : m) : 0) * g.lda;
-        if (a4 && m < g.M && kh + kq + 8 <= kend) load8(ra[hh], g.A + base + kh + kq);
-        else
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int k = kh + kq + i;
-            ra[hh][i] = (m < g.M && k < kend) ? g.A[base + k] : 0.f;
-          }
-      } else {  // 8 threads per k, 8 consecutive m each
-        const int k = kh + (t >> 3), mq = (t & 7) * 8;
-        if (a4 && k < kend && m0 + mq + 8 <= g.M) load8(ra[hh], g.A + (int64_t)k * g.lda + m0 + mq);
-        else
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int m = m0 + mq + i;
-            ra[hh][i] = (m < g.M && k < kend) ? g.A[(int64_t)k * g.lda + m] : 0.f;
-          }
-      }
-      if (g.wm == 1) {
-        const int k = kh + (t >> 3), nq = (t & 7) * 8;
-        if (w4 && k < kend && n0 + nq + 8 <= g.N) load8(rw[hh], g.W + (int64_t)k * g.ldw + n0 + nq);
-        else
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int n = n0 + nq + i;
-            rw[hh][i] = (n < g.N && k < kend) ? g.W[(int64_t)k * g.ldw + n] : 0.f;
-          }
-      } else {
-        const int r = t >> 2, kq = (t & 3) * 8, n = n0 + r;
-        if (w4 && n < g.N && kh + kq + 8 <= kend) load8(rw[hh], g.W + (int64_t)n * g.ldw + kh + kq);
-        else
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int k = kh + kq + i;
-            float v = 0.f;
-            if (n < g.N && k < kend) {
-              if (g.wm == 0) v = g.W[(int64_t)n * g.ldw + k];
-              else v = g.W[((int64_t)(k / P) * g.ldw + n) * P + (k % P)];
-            }
-            rw[hh][i] = v;
-          }
-      }
-    }
-  };
-  auto lstore = [&](int buf, float (&ra)[HH][8], float (&rw)[HH][8]) {
-#pragma unroll
-    for (int hh = 0; hh < HH; ++hh) {
-      const int ko = 32 * hh;
-      if constexpr (BF) {
-        __bf16* As = reinterpret_cast<__bf16*>(lds[buf][0]);
-        __bf16* Ws = reinterpret_cast<__bf16*>(lds[buf][1]);
-        if (!g.at) {
-          const int r = t >> 2, kq = (t & 3) * 8;
-          bf16x8 v;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = (__bf16)ra[hh][i];
-          *reinterpret_cast<bf16x8*>(As + r * TLDB + ko + kq) = v;
-        } else {
-          const int k = t >> 3, mq = (t & 7) * 8;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) As[(mq + i) * TLDB + ko + k] = (__bf16)ra[hh][i];
-        }
-        if (g.wm == 1) {
-          const int k = t >> 3, nq = (t & 7) * 8;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) Ws[(nq + i) * TLDB + ko + k] = (__bf16)rw[hh][i];
-        } else {
-          const int r = t >> 2, kq = (t & 3) * 8;
-          bf16x8 v;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = (__bf16)rw[hh][i];
-          *reinterpret_cast<bf16x8*>(Ws + r * TLDB + ko + kq) = v;
-        }
-      } else {
-        float* As = lds[buf][0];
-        float* Ws = lds[buf][1];
-        if (!g.at) {
-          const int r = t >> 2, kq = (t & 3) * 8;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) As[r * TLDK + ko + kq + i] = ra[hh][i];
-        } else {
-          const int k = t >> 3, mq = (t & 7) * 8;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) As[(mq + i) * TLDK + ko + k] = ra[hh][i];
-        }
-        if (g.wm == 1) {
-          const int k = t >> 3, nq = (t & 7) * 8;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) Ws[(nq + i) * TLDK + ko + k] = rw[hh][i];
-        } else {
-          const int r = t >> 2, kq = (t & 3) * 8;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) Ws[r * TLDK + ko + kq + i] = rw[hh][i];
-        }
-      }
-    }
-  };
-  floatx16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const int nk = (kend - kbeg + TBK - 1) / TBK;
-  auto compute = [&](int buf) {
-    if constexpr (BF) {
-      const __bf16* As = reinterpret_cast<const __bf16*>(lds[buf][0]);
-      const __bf16* Ws = reinterpret_cast<const __bf16*>(lds[buf][1]);
-#pragma unroll
-      for (int kb = 0; kb < TBK / 16; ++kb) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(As + (wmv * 32 + li) * TLDB + 16 * kb + 8 * lh);
-        const bf16x8 w = *reinterpret_cast<const bf16x8*>(Ws + (wnv * 32 + li) * TLDB + 16 * kb + 8 * lh);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, w, acc, 0, 0, 0);
-      }
-    } else {
-      const float* As = lds[buf][0];
-      const float* Ws = lds[buf][1];
-#pragma unroll
-      for (int s8 = 0; s8 < TBK / 8; ++s8) {  // lane half lh: k = (TBK / 2) lh + 4 s8 + j
-        const float4 a = *reinterpret_cast<const float4*>(As + (wmv * 32 + li) * TLDK + (TBK / 2) * lh + 4 * s8);
-        const float4 w = *reinterpret_cast<const float4*>(Ws + (wnv * 32 + li) * TLDK + (TBK / 2) * lh + 4 * s8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a, j), f4c(w, j), acc, 0, 0, 0);
-      }
-    }
-  };
-  // (loading two K steps ahead from two register sets -- 145 VGPRs, three waves per SIMD instead of
-  // four -- was bit-identical and 1-2 % slower over the training step: profiles/r06z6_train_tgemm_pf2_ab.txt)
-  gload(kbeg, ra, rw);
-  lstore(0, ra, rw);
-  __syncthreads();
-  for (int ks = 0; ks < nk; ++ks) {
-    if (ks + 1 < nk) gload(kbeg + (ks + 1) * TBK, ra, rw);
-    compute(ks & 1);
-    if (ks + 1 < nk) lstore((ks & 1) ^ 1, ra, rw);
-    __syncthreads();
-  }
-  const int col = n0 + wnv * 32 + li;
-  if (g.splits > 1) {
-    float* pt = g.part + (int64_t)split * g.M * g.N;
-    if (col < g.N)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wmv * 32 + acc_row(r, lane);
-        if (m < g.M) pt[(int64_t)m * g.N + col] = acc[r];
-      }
-    return;
-  }
-  if (col >= g.N) return;
-  const float bv = (g.bias ? g.bias[col] : 0.f) + (g.bias2 ? g.bias2[col] : 0.f);
-  // accumulate: the 16 old values are loaded together before any store (a load after a store to C
-  // may alias it, so loads interleaved with the stores each waited a full round trip: 16 per thread)
-  float* dst[16];
-  float old[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int m = m0 + wmv * 32 + acc_row(r, lane);
-    const int mc = m < g.M ? m : g.M - 1;
-    dst[r] = g.C + (int64_t)(g.crow ? g.crow[mc] : mc) * g.ldc + col;
-  }
-  if (g.accumulate) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) old[r] = m0 + wmv * 32 + acc_row(r, lane) < g.M ? *dst[r] : 0.f;
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int m = m0 + wmv * 32 + acc_row(r, lane);
-    if (m >= g.M) continue;
-    float v = acc[r] + bv;
-    if (g.act == 1) v = reluf_(v);
-    else if (g.act == 2) v = tanhf(v);
-    *dst[r] = g.accumulate ? old[r] + v : v;
-  }
-}
-
-// split-K epilogue: partials summed in split order, then bias / act / row map / accumulate
-__global__ void k_tgemm_reduce(TG g) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)g.M * g.N) return;
-  const int m = (int)(i / g.N), n = (int)(i % g.N);
-  float v = sk_sum(g.part, g.splits, (int64_t)g.M * g.N, i);
-  v += (g.bias ? g.bias[n] : 0.f) + (g.bias2 ? g.bias2[n] : 0.f);
-  if (g.act == 1) v = reluf_(v);
-  else if (g.act == 2) v = tanhf(v);
-  float* dst = g.C + (int64_t)(g.crow ? g.crow[m] : m) * g.ldc + n;
-  *dst = g.accumulate ? *dst + v : v;
-}
-
-// k_tgemm_reduce four columns per thread (16-B partial loads and stores; every element's arithmetic
-// and order exactly k_tgemm_reduce's): for N % 4 == 0 with 16-B aligned C rows, bias and partials
-// (reduce_launch checks).  The element-wise form's 4-B loads ran the largest reduce (dW_m's, 5.2 M
-// elements) at ~2 TB/s.
-__global__ void k_tgemm_reduce4(TG g) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = 4 * q;
-  if (i >= (int64_t)g.M * g.N) return;
-  const int m = (int)(i / g.N), n = (int)(i % g.N);
-  const int64_t MN = (int64_t)g.M * g.N;
-  float4 x[SK_MAX];
-#pragma unroll
-  for (int sp = 0; sp < SK_MAX; ++sp)
-    x[sp] = sp < g.splits ? *reinterpret_cast<const float4*>(g.part + sp * MN + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-  if (g.splits == 1) {
-    v[0] = x[0].x; v[1] = x[0].y; v[2] = x[0].z; v[3] = x[0].w;
-  } else {
-#pragma unroll
-    for (int sp = 0; sp < SK_MAX; ++sp)
-      if (sp < g.splits) {
-        v[0] += x[sp].x; v[1] += x[sp].y; v[2] += x[sp].z; v[3] += x[sp].w;
-      }
-    for (int sp = SK_MAX; sp < g.splits; ++sp) {
-      const float4 y = *reinterpret_cast<const float4*>(g.part + sp * MN + i);
-      v[0] += y.x; v[1] += y.y; v[2] += y.z; v[3] += y.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = v[e] + 0.f;
-  }
-  float* dst = g.C + (int64_t)(g.crow ? g.crow[m] : m) * g.ldc + n;
-  const float4 old = g.accumulate ? *reinterpret_cast<const float4*>(dst) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float r[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float t = v[e] + ((g.bias ? g.bias[n + e] : 0.f) + (g.bias2 ? g.bias2[n + e] : 0.f));
-    if (g.act == 1) t = reluf_(t);
-    else if (g.act == 2) t = tanhf(t);
-    r[e] = g.accumulate ? (&old.x)[e] + t : t;
-  }
-  *reinterpret_cast<float4*>(dst) = make_float4(r[0], r[1], r[2], r[3]);
-}
-
-// the split-K reduce of `g`: four columns per thread when the shapes and pointers allow
-static void reduce_launch(const TG& g, hipStream_t s) {
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  if (g.N % 4 == 0 && g.ldc % 4 == 0 && a16(g.C) && a16(g.part))
-    hipLaunchKernelGGL(k_tgemm_reduce4, dim3((unsigned)(((int64_t)g.M * g.N / 4 + 255) / 256)), dim3(256), 0, s, g);
-  else
-    hipLaunchKernelGGL(k_tgemm_reduce, dim3((unsigned)(((int64_t)g.M * g.N + 255) / 256)), dim3(256), 0, s, g);
-}
-
-// k_tgemm's split-K bound (floats of partials): its split counts, and so its fp32 sums, as before
-// the scratch grew for k_bgemm
-constexpr size_t TG_SPLIT_CAP = (size_t)4 << 20;
-
-// launch context of a training call: stream + split-K scratch carved from its workspace
-struct GemmCtx {
-  hipStream_t s;
-  float* split;
-  size_t cap;  // floats
-  bool bf16;   // AA_TRAIN_BF16: bf16 operands, fp32 accumulation
-  bool sent_h0 = false;  // AA_TRAIN_SENTINEL_H0: the sentinel gate without its h_{t-1} W_h term
-};
-
-// C[M,N] (+)= A W^T style helper with the common cases spelled out at the call sites.  GEMMs with
-// too few output tiles to fill the chip are split along K (deterministically reduced).
-// `defer` (the recurrent LSTM GEMMs): a split-K GEMM leaves its partial tiles in gc.split and
-// returns the split count, and the consumer (k_tr_cell_sk / k_tr_cell_bwd_sk) sums them in split order
-// itself -- k_tgemm_reduce's arithmetic, one launch fewer per recurrent step; 1 = C written (no split,
-// no bias / act / accumulate allowed with defer).
-static int tgemm(const GemmCtx& gc, int M, int N, int K, const float* A, int64_t lda, int at, const float* W, int64_t ldw,
-                 int wm, float* C, int64_t ldc, int accumulate = 0, const float* bias = nullptr,
-                 const float* bias2 = nullptr, int act = 0, const int* arow = nullptr, const int* crow = nullptr,
-                 bool defer = false) {
-  if (M <= 0 || N <= 0) return 0;
-  const hipStream_t s = gc.s;
-  static const bool tlog = [] {  // AA_TG_LOG=1: one stderr line per GEMM (shape attribution of a trace)
-    const char* e = getenv("AA_TG_LOG");
-    return e && atoi(e) == 1;
-  }();
-  if (tlog) fprintf(stderr, "tgemm M %d N %d K %d at %d wm %d acc %d stream %p\n", M, N, K, at, wm, accumulate, (void*)s);
-  const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-  int splits = 1;
-  // few tiles: split to ~256 workgroups (>= 128 deep each); long K over < 512 tiles (the vocab-sized
-  // backward GEMMs, the weight gradients over all T*B rows): split to ~1024 (>= 512 deep each)
-  const bool small = tiles < 128 && K >= 256, deep = tiles < 512 && K >= 1024;
-  // workgroups a deep split aims at (512 / 256 measured within one box's noise of 1024:
-  // profiles/r06z3_train_bgemm_split_ab.txt)
-  constexpr int deep_wg = 1024;
-  if ((small || deep) && gc.split) {
-    splits = small ? (256 + tiles - 1) / tiles : (deep_wg + tiles - 1) / tiles;
-    const int kmax = K / (small ? 128 : 512);
-    if (splits > kmax) splits = kmax;
-    const size_t capsp = (gc.cap < TG_SPLIT_CAP ? gc.cap : TG_SPLIT_CAP) / ((size_t)M * N);
-    if ((size_t)splits > capsp) splits = (int)capsp;
-    if (splits < 2) splits = 1;
-  }
-  int kper = K;
-  if (splits > 1) {
-    const int ks = gc.bf16 ? TStep<true>::KS : TStep<false>::KS;
-    kper = ((K + splits - 1) / splits + ks - 1) / ks * ks;
-    splits = (K + kper - 1) / kper;
-  }
-  // split-K partials reduced by k_tgemm_reduce unless the consumer sums them itself (defer).  (An
-  // in-launch combine by each tile's last-arriving split -- device-scope ticket, write-through
-  // partials -- was bit-identical and measured slower in round 4: 597-602 vs 683-698 steps/s.)
-  TG g{M, N, K, A, lda, arow, at, W, ldw, wm, C, ldc, crow, bias, bias2, accumulate, act, splits, kper,
-       splits > 1 ? gc.split : nullptr};
-  if (gc.bf16)
-    hipLaunchKernelGGL(k_tgemm<true>, dim3(tiles * splits), dim3(256), 0, s, g);
-  else
-    hipLaunchKernelGGL(k_tgemm<false>, dim3(tiles * splits), dim3(256), 0, s, g);
-  if (splits > 1 && !defer) reduce_launch(g, s);
-  return splits;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// The four large GEMMs of a bf16 step (vocab forward, dU = dS W_m, dW_m = dS^T U, dW_a = dV^T A) on
-// pre-packed bf16 operands: k_tgemm converted fp32 operands while staging 64 x 64 tiles (16 FLOP
-// per byte through the CU, 6-10 % of the bf16 peak on these shapes).  Here both operands are bf16,
-// row-major and K-contiguous ("NT": C[m][n] = sum_k A[m][k] B[n][k]), K a multiple of 64 with
-// zero padding, produced by the k_pk_* kernels below (RNE, the same rounding k_tgemm<true> applies
-// while staging), and a workgroup computes a 128 x 128 tile (four waves of 64 x 64 = 2 x 2
-// v_mfma_f32_32x32x16_bf16 blocks), 64-deep K steps double-buffered in LDS (144-B rows:
-// conflict-free 16-B fragment reads and staging stores).  Split-K partials go through
-// k_tgemm_reduce (fixed split order), so a step stays deterministic.
-// ---------------------------------------------------------------------------------------------
-constexpr int BG_T = 128, BG_KS = 64, BG_LD = BG_KS + 8;
-struct BG {
-  int M, N, K;
-  const __bf16* A;
-  int64_t lda;
-  const __bf16* B;
-  int64_t ldb;
-  float* C;
-  int64_t ldc;
-  const int* crow;
-  const float* bias;
-  int accumulate, splits, kper;
-  float* part;
-  int act;  // 0 none, 1 relu (after the bias)
-};
-__global__ __launch_bounds__(256, 2) void k_bgemm(BG g) {
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2][2][BG_T * BG_LD];
-  const int tilesN = (g.N + BG_T - 1) / BG_T;
-  const int split = blockIdx.x % g.splits, tile = blockIdx.x / g.splits;
-  const int mt = tile / tilesN, nt = tile % tilesN;
-  const int m0 = mt * BG_T, n0 = nt * BG_T;
-  const int kbeg = split * g.kper, kend = kbeg + g.kper < g.K ? kbeg + g.kper : g.K;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  // staging: 128 rows x 64 k per operand and step = 1024 16-B pieces, four per thread: piece
-  // q = t + 256 i -> row q >> 3, k 8 (q & 7) (8 lanes per 128-B row: coalesced loads, conflict-free
-  // ds_write_b128); rows past M / N are clamped (never stored)
-  const __bf16* pa[4];
-  const __bf16* pb[4];
-  int so[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int q = t + 256 * i, r = q >> 3, kq = (q & 7) * 8;
-    const int m = m0 + r < g.M ? m0 + r : g.M - 1, n = n0 + r < g.N ? n0 + r : g.N - 1;
-    pa[i] = g.A + (int64_t)m * g.lda + kq;
-    pb[i] = g.B + (int64_t)n * g.ldb + kq;
-    so[i] = r * BG_LD + kq;
-  }
-  bf16x8 ra[4], rb[4];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      ra[i] = *reinterpret_cast<const bf16x8*>(pa[i] + k0);
-      rb[i] = *reinterpret_cast<const bf16x8*>(pb[i] + k0);
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<bf16x8*>(&lds[buf][0][so[i]]) = ra[i];
-      *reinterpret_cast<bf16x8*>(&lds[buf][1][so[i]]) = rb[i];
-    }
-  };
-  floatx16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
-  const int nk = (kend - kbeg) / BG_KS;
-  gload(kbeg);
-  lstore(0);
-  __syncthreads();
-  for (int ks = 0; ks < nk; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nk) gload(kbeg + (ks + 1) * BG_KS);
-    const __bf16* As = lds[buf][0];
-    const __bf16* Bs = lds[buf][1];
-#pragma unroll
-    for (int kb = 0; kb < BG_KS / 16; ++kb) {
-      bf16x8 a[2], b[2];
-#pragma unroll
-      for (int x = 0; x < 2; ++x) a[x] = *reinterpret_cast<const bf16x8*>(As + (wm * 64 + x * 32 + li) * BG_LD + 16 * kb + 8 * lh);
-#pragma unroll
-      for (int y = 0; y < 2; ++y) b[y] = *reinterpret_cast<const bf16x8*>(Bs + (wn * 64 + y * 32 + li) * BG_LD + 16 * kb + 8 * lh);
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x], b[y], acc[x][y], 0, 0, 0);
-    }
-    if (ks + 1 < nk) lstore(buf ^ 1);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int y = 0; y < 2; ++y) {
-    const int col = n0 + wn * 64 + y * 32 + li;
-    if (col >= g.N) continue;
-    const float bv = g.bias ? g.bias[col] : 0.f;
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + x * 32 + acc_row(r, lane);
-        if (m >= g.M) continue;
-        if (g.splits > 1) {
-          g.part[(int64_t)split * g.M * g.N + (int64_t)m * g.N + col] = acc[x][y][r];
-        } else {
-          float v = acc[x][y][r] + bv;
-          if (g.act == 1) v = reluf_(v);
-          float* dst = g.C + (int64_t)(g.crow ? g.crow[m] : m) * g.ldc + col;
-          *dst = g.accumulate ? *dst + v : v;
-        }
-      }
-  }
-}
-
-// dst[r][k] = bf16(src[map ? map[r] : r][k]) for k < cols, 0 up to Kp (a multiple of 8): 8 per thread,
-// as two 16-B loads when the source rows allow (vec: lds % 4 == 0, cols % 8 == 0, 16-B aligned base)
-__global__ void k_pk_rows(const float* __restrict__ src, int64_t lds, const int* __restrict__ map, int rows, int cols,
-                          __bf16* __restrict__ dst, int Kp, int vec) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int per = Kp / 8;
-  if (i >= (int64_t)rows * per) return;
-  const int r = (int)(i / per), k0 = (int)(i % per) * 8;
-  const float* sr = src + (int64_t)(map ? map[r] : r) * lds;
-  bf16x8 v;
-  if (vec && k0 < cols) {
-    const float4 x = *reinterpret_cast<const float4*>(sr + k0), y = *reinterpret_cast<const float4*>(sr + k0 + 4);
-    v[0] = (__bf16)x.x; v[1] = (__bf16)x.y; v[2] = (__bf16)x.z; v[3] = (__bf16)x.w;
-    v[4] = (__bf16)y.x; v[5] = (__bf16)y.y; v[6] = (__bf16)y.z; v[7] = (__bf16)y.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)(k0 + j < cols ? sr[k0 + j] : 0.f);
-  }
-  *reinterpret_cast<bf16x8*>(dst + (int64_t)r * Kp + k0) = v;
-}
-
-// transpose: dst[c][r] = bf16(src[r lds + c]) for r < rows, 0 for rows <= r < Kp; dst has cols rows
-// of Kp.  64 x 64 tiles through LDS (reads along c, writes along r, both coalesced).  S: float or
-// __bf16 (a bf16 source is already rounded: the same values)
-template <class S>
-__global__ __launch_bounds__(256) void k_pk_trans(const S* __restrict__ src, int64_t lds, int rows, int cols,
-                                                  __bf16* __restrict__ dst, int Kp) {
-  __shared__ float tile[64][65];
-  const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64, t = threadIdx.x;
-  for (int i = t; i < 64 * 64; i += 256) {
-    const int rr = i / 64, cc = i % 64, r = r0 + rr, c = c0 + cc;
-    tile[rr][cc] = (r < rows && c < cols) ? (float)src[(int64_t)r * lds + c] : 0.f;
-  }
-  __syncthreads();
-  for (int i = t; i < 64 * 64; i += 256) {
-    const int cc = i / 64, rr = i % 64, c = c0 + cc, r = r0 + rr;
-    if (c < cols && r < Kp) dst[(int64_t)c * Kp + r] = (__bf16)tile[rr][cc];
-  }
-}
-
-// the NCHW feature map as the bf16 row matrix of the encoder GEMM V = relu(A W_a^T + b): dst[b 49 + p][c]
-// = feats[b][c][p]; a workgroup per (image, 64 channels) reads its 64 x 49 contiguous floats and writes
-// 49 rows of 128 B
-__global__ __launch_bounds__(256) void k_pk_featrows(const float* __restrict__ feats, int C, __bf16* __restrict__ dst) {
-  __shared__ float tile[64 * P];
-  const int b = blockIdx.y, c0 = blockIdx.x * 64, t = threadIdx.x;
-  const float* src = feats + ((int64_t)b * C + c0) * P;
-  for (int i = t; i < 64 * P; i += 256) tile[i] = src[i];  // [c][p]
-  __syncthreads();
-  for (int i = t; i < P * 8; i += 256) {  // row p, 8-channel piece j
-    const int p = i >> 3, j = i & 7;
-    bf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (__bf16)tile[(8 * j + e) * P + p];
-    *reinterpret_cast<bf16x8*>(dst + ((int64_t)b * P + p) * C + c0 + 8 * j) = v;
-  }
-}
-
-// One pass over the NCHW feature map for a bf16 step: a workgroup per (image, 64 channels) reads its
-// 64 x 49 contiguous floats once and writes (1) the rows of the encoder GEMM's operand, as
-// k_pk_featrows; (2) the K-contiguous operand of the backward's dW_a = dV^T A, cols[c][b 49 + p] (as
-// k_pk_feats, zero past row B 49 up to Kp: the last image's workgroups); (3) a_g[b][c] = the 49 values
-// summed in p order / 49 -- k_avgpool's arithmetic, bit-identical.  Replaces k_avgpool +
-// k_pk_featrows + the backward's k_pk_feats (three reads of the map, one now).
-__global__ __launch_bounds__(256) void k_pk_feats3(const float* __restrict__ feats, int B, int C,
-                                                   __bf16* __restrict__ rows, __bf16* __restrict__ cols, int Kp,
-                                                   float* __restrict__ a_g) {
-  __shared__ float tile[64 * P];
-  const int b = blockIdx.y, c0 = blockIdx.x * 64, t = threadIdx.x;
-  const float* src = feats + ((int64_t)b * C + c0) * P;
-  for (int i = t; i < 64 * P; i += 256) tile[i] = src[i];  // [c][p]
-  __syncthreads();
-  for (int i = t; i < P * 8; i += 256) {  // row p, 8-channel piece j
-    const int p = i >> 3, j = i & 7;
-    bf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (__bf16)tile[(8 * j + e) * P + p];
-    *reinterpret_cast<bf16x8*>(rows + ((int64_t)b * P + p) * C + c0 + 8 * j) = v;
-  }
-  for (int i = t; i < 64 * P; i += 256) {
-    const int c = i / P, p = i - c * P;
-    cols[(int64_t)(c0 + c) * Kp + b * P + p] = (__bf16)tile[i];
-  }
-  if (b == B - 1)
-    for (int i = t; i < 64 * (Kp - B * P); i += 256) {
-      const int c = i / (Kp - B * P), r = B * P + i % (Kp - B * P);
-      cols[(int64_t)(c0 + c) * Kp + r] = (__bf16)0.f;
-    }
-  if (t < 64) {
-    const float* g = tile + t * P;
-    float sum = 0.f;
-    for (int p = 0; p < P; ++p) sum += g[p];
-    a_g[(int64_t)b * C + c0 + t] = sum / 49.0f;
-  }
-}
-
-// the NCHW feature map as the K-contiguous operand of dW_a = dV^T A: dst[c][b 49 + p] = feats[b][c][p],
-// zero for rows >= B 49 up to Kp; 8 consecutive rows per thread (one 16-B store)
-__global__ void k_pk_feats(const float* __restrict__ feats, int B, int C, __bf16* __restrict__ dst, int Kp) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int per = Kp / 8;
-  if (i >= (int64_t)C * per) return;
-  const int c = (int)(i / per), row0 = (int)(i % per) * 8;
-  bf16x8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int row = row0 + j;
-    float x = 0.f;
-    if (row < B * P) {
-      const int b = row / P, p = row - b * P;
-      x = feats[((int64_t)b * C + c) * P + p];
-    }
-    v[j] = (__bf16)x;
-  }
-  *reinterpret_cast<bf16x8*>(dst + (int64_t)c * Kp + row0) = v;
-}
-
-// C[M,N] (+)= A B^T (+ bias) on k_bgemm; K a multiple of 64.  Fewer than 512 tiles: split K to
-// ~256 workgroups (bounded by the split scratch), partials reduced by k_tgemm_reduce in split order.
-static void bgemm(const GemmCtx& gc, int M, int N, int K, const __bf16* A, int64_t lda, const __bf16* B, int64_t ldb,
-                  float* C, int64_t ldc, const float* bias = nullptr, const int* crow = nullptr, int accumulate = 0,
-                  int act = 0) {
-  if (M <= 0 || N <= 0 || K <= 0) return;
-  const int tiles = ((M + BG_T - 1) / BG_T) * ((N + BG_T - 1) / BG_T), ksteps = K / BG_KS;
-  // workgroups a split launch aims at: 64 / 128 / 192 / 512 / 1024 / 2048 measured no better (at 1024
-  // dU's split writes 18 partial sets where 256 writes 5: profiles/r06z3_train_bgemm_split_ab.txt)
-  constexpr int wg_target = 256;
-  int splits = tiles >= 512 ? 1 : (wg_target + tiles - 1) / tiles;
-  if (splits > ksteps) splits = ksteps;
-  const size_t capsp = gc.split ? gc.cap / ((size_t)M * N) : 1;
-  if ((size_t)splits > capsp) splits = (int)capsp;
-  if (splits < 1) splits = 1;
-  const int kper = (ksteps + splits - 1) / splits * BG_KS;
-  splits = (K + kper - 1) / kper;
-  const BG g{M, N, K, A, lda, B, ldb, C, ldc, crow, bias, accumulate, splits, kper, splits > 1 ? gc.split : nullptr, act};
-  hipLaunchKernelGGL(k_bgemm, dim3(tiles * splits), dim3(256), 0, gc.s, g);
-  if (splits > 1) {
-    TG r{};
-    r.M = M; r.N = N; r.K = K; r.C = C; r.ldc = ldc; r.crow = crow; r.bias = bias; r.accumulate = accumulate;
-    r.splits = splits; r.kper = kper; r.part = gc.split; r.act = act;
-    reduce_launch(r, gc.s);
-  }
-}
-static inline int rup64(int x) { return (x + 63) / 64 * 64; }
-static void pk_rows(hipStream_t st, const float* src, int64_t lds, const int* map, int rows, int cols, __bf16* dst, int Kp) {
-  const int64_t n = (int64_t)rows * (Kp / 8);
-  const int vec = lds % 4 == 0 && cols % 8 == 0 && ((uintptr_t)src & 15) == 0;
-  hipLaunchKernelGGL(k_pk_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, lds, map, rows, cols, dst, Kp,
-                     vec);
-}
-template <class S>
-static void pk_trans(hipStream_t st, const S* src, int64_t lds, int rows, int cols, __bf16* dst, int Kp) {
-  hipLaunchKernelGGL(k_pk_trans<S>, dim3((unsigned)(Kp / 64), (unsigned)((cols + 63) / 64)), dim3(256), 0, st, src, lds,
-                     rows, cols, dst, Kp);
-}
-
-// column sums: out[n] (+)= sum_m X[m ldx + n], deterministic: rows split into CS_CH fixed chunks
-// summed in order by k_colsum (one thread per (column, chunk)), the chunk sums added in chunk
-// order by k_colsum_fin.
-constexpr int CS_CH = 64;
-__global__ void k_colsum(const float* __restrict__ X, int M, int N, int64_t ldx, float* __restrict__ part) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
-  if (n >= N) return;
-  const int per = (M + CS_CH - 1) / CS_CH, m0 = ch * per, m1 = m0 + per < M ? m0 + per : M;
-  float s = 0.f;
-  int m = m0;
-  // eight loads in flight, then the eight adds in row order (the same sum, bit for bit, as one row
-  // at a time; a chunk of 98 rows -- the dV bias gradient -- ran ~30 us one dependent load at a time)
-  for (; m + 8 <= m1; m += 8) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = X[(int64_t)(m + j) * ldx + n];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += x[j];
-  }
-  for (; m < m1; ++m) s += X[(int64_t)m * ldx + n];
-  part[(int64_t)ch * N + n] = s;
-}
-__global__ void k_colsum_fin(const float* __restrict__ part, int N, float* __restrict__ out) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  float s = 0.f;
-  for (int ch = 0; ch < CS_CH; ++ch) s += part[(int64_t)ch * N + n];
-  out[n] = s;
-}
-// k_colsum + k_colsum_fin in one launch for short columns (M <= CS1_MAXM: the encoder-head bias
-// gradients over the B rows): a workgroup per 64 columns, wave g sums chunks [16 g, 16 g + 16) of
-// its lane's column (k_colsum's chunks, rows in order from 0), the 64 chunk sums go through LDS and
-// lane c of wave 0 adds them in chunk order from 0 -- k_colsum_fin's arithmetic: the same bits, one
-// launch instead of two, every load of a thread in flight at once.
-constexpr int CS1_MAXM = 512;
-__global__ __launch_bounds__(256) void k_colsum1(const float* __restrict__ X, int M, int N, int64_t ldx,
-                                                 float* __restrict__ out) {
-  __shared__ float cs[CS_CH][65];
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6, n = blockIdx.x * 64 + c;
-  const int per = (M + CS_CH - 1) / CS_CH;
-  const int nc = n < N ? n : N - 1;
-  for (int j = 0; j < CS_CH / 4; ++j) {
-    const int ch = 16 * g + j, m0 = ch * per, m1 = m0 + per < M ? m0 + per : M;
-    float x[CS1_MAXM / CS_CH];
-#pragma unroll
-    for (int i = 0; i < CS1_MAXM / CS_CH; ++i) x[i] = m0 + i < m1 ? X[(int64_t)(m0 + i) * ldx + nc] : 0.f;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < CS1_MAXM / CS_CH; ++i)
-      if (m0 + i < m1) s += x[i];
-    cs[ch][c] = s;
-  }
-  __syncthreads();
-  if (g == 0 && n < N) {
-    float s = 0.f;
-    for (int ch = 0; ch < CS_CH; ++ch) s += cs[ch][c];
-    out[n] = s;
-  }
-}
-static void colsum(hipStream_t st, const float* X, int M, int N, int64_t ldx, float* scratch, float* out) {
-  if (M > 0 && M <= CS1_MAXM) {
-    hipLaunchKernelGGL(k_colsum1, dim3((N + 63) / 64), dim3(256), 0, st, X, M, N, ldx, out);
-    return;
-  }
-  hipLaunchKernelGGL(k_colsum, dim3((N + 255) / 256, CS_CH), dim3(256), 0, st, X, M, N, ldx, scratch);
-  hipLaunchKernelGGL(k_colsum_fin, dim3((N + 255) / 256), dim3(256), 0, st, scratch, N, out);
-}
 
 // Two streams of one training call: `main` (the caller's) carries the chain the result depends on
 // step by step (encoder head -> LSTM -> attention -> vocab; its backward in reverse), `aux` the
@@ -1551,7 +819,17 @@ __global__ __launch_bounds__(256) void k_wT(WTArgs a) {
   }
 }
 
+// buffers one memset or one launch treats as a single array: carved as one piece (carve_train's group)
+struct Span {
+  float* p;
+  size_t n;  // floats
+  size_t bytes() const { return n * sizeof(float); }
+};
+
 struct TrainWS {
+  Span hc0;        // h0 | c0
+  Span att_grads;  // dU | dS | dPG | dPS
+  Span rec;        // dh_rec | dc_rec
   float *a_g, *V, *vg, *h0, *c0, *VWv, *X, *PRE, *G4, *GA, *Hs, *Cs, *SG, *S, *PG, *PS, *alpha, *beta, *ctx, *U;
   int* prow;
   // backward scratch
@@ -1585,11 +863,27 @@ static TrainWS carve_train(char* base, const aa_dims& d, int B, int T, int Nmax,
   Carver c{base};
   const size_t H = d.hidden, E = d.embed, Cc = d.channels, R = (size_t)T * B, P_ = aa::P, PP_ = aa::PP;
   TrainWS w;
+  // members of a group back to back by construction.  Each is a whole number of the Carver's 256-B
+  // granules (hidden % 256 == 0: train_check; PP == 64), so the offsets are those of a take per member.
+  static_assert(aa::PP * sizeof(float) % 256 == 0, "a PP-pitched row is whole 256-B granules");
+  const auto group = [&c](std::initializer_list<std::pair<float**, size_t>> members) {
+    Span g{nullptr, 0};
+    for (const auto& m : members) {
+      assert(m.second * sizeof(float) % 256 == 0);
+      g.n += m.second;
+    }
+    g.p = c.take<float>(g.n);
+    size_t o = 0;
+    for (const auto& m : members) {
+      *m.first = g.p ? g.p + o : nullptr;
+      o += m.second;
+    }
+    return g;
+  };
   w.a_g = c.take<float>(B * Cc);
   w.V = c.take<float>(B * P_ * H);
   w.vg = c.take<float>(B * E);
-  w.h0 = c.take<float>(B * H);
-  w.c0 = c.take<float>(B * H);
+  w.hc0 = group({{&w.h0, B * H}, {&w.c0, B * H}});
   w.VWv = c.take<float>(B * P_ * PP_);
   w.X = c.take<float>(R * 2 * E);
   w.PRE = c.take<float>(R * 5 * H);
@@ -1607,10 +901,7 @@ static TrainWS carve_train(char* base, const aa_dims& d, int B, int T, int Nmax,
   w.U = c.take<float>(R * H);
   w.prow = c.take<int>(R);
   w.Up = c.take<float>((size_t)Nmax * H);
-  w.dU = c.take<float>(R * H);
-  w.dS = c.take<float>(R * H);
-  w.dPG = c.take<float>(R * PP_);
-  w.dPS = c.take<float>(R * PP_);
+  w.att_grads = group({{&w.dU, R * H}, {&w.dS, R * H}, {&w.dPG, R * PP_}, {&w.dPS, R * PP_}});
   w.dV = c.take<float>(B * P_ * H);
   w.dVWv = c.take<float>(B * P_ * PP_);
   w.dwh = c.take<float>(B * PP_);
@@ -1619,8 +910,7 @@ static TrainWS carve_train(char* base, const aa_dims& d, int B, int T, int Nmax,
   w.dG = c.take<float>(R * H);
   w.DG = c.take<float>(R * 4 * H);
   w.dX = c.take<float>(R * 2 * E);
-  w.dh_rec = c.take<float>(B * H);
-  w.dc_rec = c.take<float>(B * H);
+  w.rec = group({{&w.dh_rec, B * H}, {&w.dc_rec, B * H}});
   w.dvg = c.take<float>(B * E);
   w.dA = c.take<float>(B * P_ * Cc);
   w.dag = c.take<float>(B * Cc);
@@ -1680,6 +970,29 @@ size_t aa_train_workspace_bytes(const aa_dims* d, int32_t B, int32_t T) {
   return n;
 }
 
+// The argument checks every entry point makes, in their order of precedence: dims / B / T
+// (train_check), nothing to do (AA_OK), the call's own null-pointer list, its own shape list, then the
+// carve and the workspace size.  False: return *rc; true: *s is the carved workspace.
+struct TrainArgs {
+  const aa_dims* dims;
+  int B, T;
+  bool empty = false;  // beyond B == 0 || T == 0
+  bool null, shape;    // a required pointer is null / a shape is inconsistent
+  void* workspace;
+  size_t workspace_bytes;
+};
+static bool train_args(const TrainArgs& a, TrainWS* s, int* rc) {
+  *rc = train_check(a.dims, a.B, a.T);
+  if (*rc) return false;
+  if (a.B == 0 || a.T == 0 || a.empty) return false;  // AA_OK
+  size_t need = 0;
+  if (a.null) *rc = AA_ERR_NULL;
+  else if (a.shape) *rc = AA_ERR_SHAPE;
+  else *s = carve_train(static_cast<char*>(a.workspace), *a.dims, a.B, a.T, a.B * a.T, &need);
+  if (!*rc && a.workspace_bytes < need) *rc = AA_ERR_BUFFER;
+  return !*rc;
+}
+
 static inline unsigned nblk(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 // Decoder.forward over T teacher-forced steps (baseline_attention.py:148-194 with the adaptive
@@ -1694,8 +1007,10 @@ static void decoder_core(const GemmCtx& gc, const aa_ref_weights* w, const Train
   const hipStream_t st = gc.s;
   // x_t and the step-invariant input terms for all steps
   hipLaunchKernelGGL(k_tr_x, dim3(R), dim3(256), 0, st, tokens, tok_ld, w->embed_w, V, E, s.vg, B, T, s.X);
-  tgemm(gc, R, 4 * H, 2 * E, s.X, 2 * E, 0, w->lstm_w_ih, 2 * E, 0, s.PRE, 5 * H, 0, w->lstm_b_ih, w->lstm_b_hh);
-  tgemm(gc, R, H, 2 * E, s.X, 2 * E, 0, w->sent_affine_x_w, 2 * E, 0, s.PRE + 4 * H, 5 * H);
+  tgemm(gc, {.M = R, .N = 4 * H, .K = 2 * E, .A = s.X, .lda = 2 * E, .W = w->lstm_w_ih, .ldw = 2 * E, .C = s.PRE,
+             .ldc = 5 * H, .bias = w->lstm_b_ih, .bias2 = w->lstm_b_hh});
+  tgemm(gc, {.M = R, .N = H, .K = 2 * E, .A = s.X, .lda = 2 * E, .W = w->sent_affine_x_w, .ldw = 2 * E,
+             .C = s.PRE + 4 * H, .ldc = 5 * H});
   // LSTM over T steps (baseline_attention.py:167-178)
   if (gc.bf16) {
     // one fused launch per step (k_tr_lstm_f), W_hh packed to bf16 fragments once
@@ -1705,21 +1020,20 @@ static void decoder_core(const GemmCtx& gc, const aa_ref_weights* w, const Train
       const float* cp = t ? s.Cs + (size_t)(t - 1) * B * H : s.c0;
       const float* pre = s.PRE + (size_t)t * B * 5 * H;
       float *ho = s.Hs + (size_t)t * B * H, *co = s.Cs + (size_t)t * B * H, *ga = s.GA + (size_t)t * B * 4 * H;
+      // step 0 reads h0 (fp32), a later step the bf16 copy of h the step before it wrote
+      const bool first = t == 0;
+      const void* hp = first ? (const void*)s.h0 : (const void*)s.hb[(t - 1) & 1];
       aa_for_hidden(H, [&](auto h) {
-        if (t == 0)
-          hipLaunchKernelGGL((k_tr_lstm_f<h.value, true>), dim3(grid), dim3(256), 0, st, B, (const void*)s.h0, pre,
-                             5 * H, cp, s.whf, ho, co, ga, s.hb[0]);
-        else
-          hipLaunchKernelGGL((k_tr_lstm_f<h.value, false>), dim3(grid), dim3(256), 0, st, B,
-                             (const void*)s.hb[(t - 1) & 1], pre, 5 * H, cp, s.whf, ho, co, ga, s.hb[t & 1]);
+        const auto k = first ? k_tr_lstm_f<h.value, true> : k_tr_lstm_f<h.value, false>;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, B, hp, pre, 5 * H, cp, s.whf, ho, co, ga, s.hb[t & 1]);
       });
     }
   } else {
     for (int t = 0; t < T; ++t) {
       const float* hp = t ? s.Hs + (size_t)(t - 1) * B * H : s.h0;
       const float* cp = t ? s.Cs + (size_t)(t - 1) * B * H : s.c0;
-      const int S = tgemm(gc, B, 4 * H, H, hp, H, 0, w->lstm_w_hh, H, 0, s.G4, 4 * H, 0, nullptr, nullptr, 0, nullptr,
-                          nullptr, true);
+      const int S = tgemm(gc, {.M = B, .N = 4 * H, .K = H, .A = hp, .lda = H, .W = w->lstm_w_hh, .ldw = H, .C = s.G4,
+                               .ldc = 4 * H}, TG_DEFER);
       hipLaunchKernelGGL(k_tr_cell_sk, dim3(nblk((int64_t)B * H)), dim3(256), 0, st, S > 1 ? gc.split : s.G4, S,
                          s.PRE + (size_t)t * B * 5 * H, 5 * H, cp, B, H, s.Hs + (size_t)t * B * H,
                          s.Cs + (size_t)t * B * H, s.GA + (size_t)t * B * 4 * H);
@@ -1729,11 +1043,12 @@ static void decoder_core(const GemmCtx& gc, const aa_ref_weights* w, const Train
   hipLaunchKernelGGL(k_copy_cols, dim3(nblk((int64_t)R * H)), dim3(256), 0, st, s.PRE, (int64_t)5 * H, 4 * H, s.SG,
                      (int64_t)H, R, H);
   // (AA_TRAIN_SENTINEL_H0: no rows, as at T = 1 -- the gate of the one-token decode step, every step)
-  tgemm(gc, gc.sent_h0 ? 0 : R - B, H, H, s.Hs, H, 0, w->sent_affine_h_w, H, 0, s.SG + (size_t)B * H, H, 1);
+  tgemm(gc, {.M = gc.sent_h0 ? 0 : R - B, .N = H, .K = H, .A = s.Hs, .lda = H, .W = w->sent_affine_h_w, .ldw = H,
+             .C = s.SG + (size_t)B * H, .ldc = H, .accumulate = true});
   hipLaunchKernelGGL(k_tr_sent, dim3(nblk((int64_t)R * H)), dim3(256), 0, st, s.SG, s.Cs, s.S, (int64_t)R * H);
   // attention projections and the attention itself (adaptive_attention.py:26-58)
-  tgemm(gc, R, P, H, s.Hs, H, 0, w->att_affine_g_w, H, 0, s.PG, PP);
-  tgemm(gc, R, P, H, s.S, H, 0, w->att_affine_s_w, H, 0, s.PS, PP);
+  tgemm(gc, {.M = R, .N = P, .K = H, .A = s.Hs, .lda = H, .W = w->att_affine_g_w, .ldw = H, .C = s.PG, .ldc = PP});
+  tgemm(gc, {.M = R, .N = P, .K = H, .A = s.S, .lda = H, .W = w->att_affine_s_w, .ldw = H, .C = s.PS, .ldc = PP});
   if (join) join->to_main();
   // rows grouped by image (V_b read once per group): groups of TS steps so that the grid covers
   // the chip (>= 256 workgroups when B is small)
@@ -1760,36 +1075,36 @@ int aa_train_forward_aux(const aa_ref_weights* w, const aa_dims* dims, const flo
                          void* workspace, size_t workspace_bytes, int32_t flags, aa_stream_t stream,
                          aa_stream_t aux) {
   using namespace aa;
-  int rc = train_check(dims, B, T);
-  if (rc) return rc;
-  if (B == 0 || T == 0 || N == 0) return AA_OK;
-  if (!w || !feats || !tokens || !lengths || !scores || !workspace || !w->sent_affine_h_w) return AA_ERR_NULL;
-  if (N > B * T || tok_ld < T) return AA_ERR_SHAPE;
-  size_t need;
-  TrainWS s = carve_train(static_cast<char*>(workspace), *dims, B, T, B * T, &need);
-  if (workspace_bytes < need) return AA_ERR_BUFFER;
+  TrainWS s;
+  int rc;
+  if (!train_args({.dims = dims, .B = B, .T = T, .empty = N == 0,
+                   .null = !w || !feats || !tokens || !lengths || !scores || !workspace || !w->sent_affine_h_w,
+                   .shape = N > B * T || tok_ld < T, .workspace = workspace, .workspace_bytes = workspace_bytes},
+                  &s, &rc))
+    return rc;
   const int H = dims->hidden, E = dims->embed, C = dims->channels, V = dims->vocab, R = T * B;
   hipStream_t st = (hipStream_t)stream;
   Fork f(st, (hipStream_t)aux);
-  const bool bf = (flags & AA_TRAIN_BF16) != 0;
-  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, bf, (flags & AA_TRAIN_SENTINEL_H0) != 0};
-  const GemmCtx ga{f.aux, s.gsplit2, TR_SPLIT_FLOATS, bf};
+  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, (flags & AA_TRAIN_BF16) != 0, (flags & AA_TRAIN_SENTINEL_H0) != 0};
+  const GemmCtx ga{f.aux, s.gsplit2, TR_SPLIT_FLOATS, gc.bf16};
   // encoder tail (baseline_attention.py:46-60), reference weight layouts: a_g and the heads on the
   // main stream (the LSTM needs them), the spatial V = relu(A W_a^T + b) and VWv on aux beside the
   // LSTM (the attention is their first reader)
-  if (gc.bf16 && H % 64 == 0 && C % 64 == 0) {
+  if (gc.bf16) {
     // bf16 step: V on k_bgemm; one pass over the feature map packs both bf16 operand layouts (this
     // GEMM's rows, the backward's dW_a columns) and computes a_g
-    hipLaunchKernelGGL(k_pk_feats3, dim3(C / 64, B), dim3(256), 0, st, feats, B, C, s.ftT, s.ftC, rup64(B * P), s.a_g);
+    pk_feats3(st, feats, B, C, s.ftT, s.ftC, s.a_g);
     f.to_aux();
     pk_rows(ga.s, w->enc_affine_a_w, C, nullptr, H, C, s.wmT, C);
-    bgemm(ga, B * P, H, C, s.ftT, C, s.wmT, C, s.V, H, w->enc_affine_a_b, nullptr, 0, 1);
+    bgemm(ga, {.M = B * P, .N = H, .K = C, .A = s.ftT, .lda = C, .B = s.wmT, .ldb = C, .C = s.V, .ldc = H,
+               .bias = w->enc_affine_a_b, .act = ACT_RELU});
   } else {
     avgpool_launch(feats, (int64_t)B * C, s.a_g, st);
     f.to_aux();
     enc_v_launch(feats, B, C, H, w->enc_affine_a_w, w->enc_affine_a_b, s.V, ga.s);
   }
-  tgemm(ga, B * P, P, H, s.V, H, 0, w->att_affine_v_w, H, 0, s.VWv, PP);  // VWv = V W_v^T
+  tgemm(ga, {.M = B * P, .N = P, .K = H, .A = s.V, .lda = H, .W = w->att_affine_v_w, .ldw = H, .C = s.VWv,
+             .ldc = PP});  // VWv = V W_v^T
   // the packed rows of the scores (pack_padded_sequence order), also off the chain
   hipLaunchKernelGGL(k_tr_prow, dim3(nblk(R)), dim3(256), 0, ga.s, lengths, B, T, s.prow);
   // the backward's transposed weights, off the chain too (the parameters do not change until the
@@ -1810,18 +1125,23 @@ int aa_train_forward_aux(const aa_ref_weights* w, const aa_dims* dims, const flo
     a.blk0[a.n] = tiles;
     hipLaunchKernelGGL(k_wT, dim3(tiles), dim3(256), 0, ga.s, a);
   }
-  tgemm(gc, B, E, C, s.a_g, C, 0, w->enc_affine_b_w, C, 0, s.vg, E, 0, w->enc_affine_b_b, nullptr, 1);
-  tgemm(gc, B, H, C, s.a_g, C, 0, w->enc_affine_h0_w, C, 0, s.h0, H, 0, w->enc_affine_h0_b, nullptr, 2);
-  tgemm(gc, B, H, C, s.a_g, C, 0, w->enc_affine_c0_w, C, 0, s.c0, H, 0, w->enc_affine_c0_b, nullptr, 2);
+  tgemm(gc, {.M = B, .N = E, .K = C, .A = s.a_g, .lda = C, .W = w->enc_affine_b_w, .ldw = C, .C = s.vg, .ldc = E,
+             .bias = w->enc_affine_b_b, .act = ACT_RELU});
+  tgemm(gc, {.M = B, .N = H, .K = C, .A = s.a_g, .lda = C, .W = w->enc_affine_h0_w, .ldw = C, .C = s.h0, .ldc = H,
+             .bias = w->enc_affine_h0_b, .act = ACT_TANH});
+  tgemm(gc, {.M = B, .N = H, .K = C, .A = s.a_g, .lda = C, .W = w->enc_affine_c0_w, .ldw = C, .C = s.c0, .ldc = H,
+             .bias = w->enc_affine_c0_b, .act = ACT_TANH});
   decoder_core(gc, w, s, *dims, B, T, tokens, tok_ld, &f);
   if (f.err) return (int)f.err;
   // packed scores = mlp(c_hat + h) on the packed rows (:132, baseline_attention.py:228)
-  if (gc.bf16 && H % 64 == 0) {
+  if (gc.bf16) {
     pk_rows(st, s.U, H, s.prow, N, H, s.ub, H);
     pk_rows(st, w->mlp_w, H, nullptr, V, H, s.wmb, H);
-    bgemm(gc, N, V, H, s.ub, H, s.wmb, H, scores, V, w->mlp_b);
+    bgemm(gc, {.M = N, .N = V, .K = H, .A = s.ub, .lda = H, .B = s.wmb, .ldb = H, .C = scores, .ldc = V,
+               .bias = w->mlp_b});
   } else {
-    tgemm(gc, N, V, H, s.U, H, 0, w->mlp_w, H, 0, scores, V, 0, w->mlp_b, nullptr, 0, s.prow);
+    tgemm(gc, {.M = N, .N = V, .K = H, .A = s.U, .lda = H, .arow = s.prow, .W = w->mlp_w, .ldw = H, .C = scores,
+               .ldc = V, .bias = w->mlp_b});
   }
   return aa_launch_status();
 }
@@ -1856,14 +1176,13 @@ int aa_decoder_forward(const aa_ref_weights* w, const aa_dims* dims, const float
                        float* scores, float* alpha, float* beta, float* h_out, float* c_out, void* workspace,
                        size_t workspace_bytes, int32_t flags, aa_stream_t stream) {
   using namespace aa;
-  int rc = train_check(dims, B, T);
-  if (rc) return rc;
-  if (B == 0 || T == 0) return AA_OK;
-  if (!w || !V || !v_g || !h0 || !c0 || !tokens || !workspace || !w->sent_affine_h_w) return AA_ERR_NULL;
-  if (tok_ld < T) return AA_ERR_SHAPE;
-  size_t need;
-  TrainWS s = carve_train(static_cast<char*>(workspace), *dims, B, T, B * T, &need);
-  if (workspace_bytes < need) return AA_ERR_BUFFER;
+  TrainWS s;
+  int rc;
+  if (!train_args({.dims = dims, .B = B, .T = T,
+                   .null = !w || !V || !v_g || !h0 || !c0 || !tokens || !workspace || !w->sent_affine_h_w,
+                   .shape = tok_ld < T, .workspace = workspace, .workspace_bytes = workspace_bytes},
+                  &s, &rc))
+    return rc;
   const int H = dims->hidden, E = dims->embed, Vc = dims->vocab, R = T * B;
   hipStream_t st = (hipStream_t)stream;
   const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, (flags & AA_TRAIN_BF16) != 0, (flags & AA_TRAIN_SENTINEL_H0) != 0};
@@ -1873,11 +1192,13 @@ int aa_decoder_forward(const aa_ref_weights* w, const aa_dims* dims, const float
   if (!e) e = hipMemcpyAsync(s.h0, h0, sizeof(float) * (size_t)B * H, hipMemcpyDeviceToDevice, st);
   if (!e) e = hipMemcpyAsync(s.c0, c0, sizeof(float) * (size_t)B * H, hipMemcpyDeviceToDevice, st);
   if (e) return (int)e;
-  tgemm(gc, B * P, P, H, s.V, H, 0, w->att_affine_v_w, H, 0, s.VWv, PP);  // VWv = V W_v^T
+  tgemm(gc, {.M = B * P, .N = P, .K = H, .A = s.V, .lda = H, .W = w->att_affine_v_w, .ldw = H, .C = s.VWv,
+             .ldc = PP});  // VWv = V W_v^T
   decoder_core(gc, w, s, *dims, B, T, tokens, tok_ld);
   if (scores) {  // mlp(c_hat + h) for every (b, t), batch-first (:132)
     hipLaunchKernelGGL(k_bt_rowmap, dim3(nblk(R)), dim3(256), 0, st, B, T, s.prow);
-    tgemm(gc, R, Vc, H, s.U, H, 0, w->mlp_w, H, 0, scores, Vc, 0, w->mlp_b, nullptr, 0, nullptr, s.prow);
+    tgemm(gc, {.M = R, .N = Vc, .K = H, .A = s.U, .lda = H, .W = w->mlp_w, .ldw = H, .C = scores, .ldc = Vc,
+               .crow = s.prow, .bias = w->mlp_b});
   }
   if (alpha || beta)
     hipLaunchKernelGGL(k_bt_atten_out, dim3(nblk((int64_t)R * (P + 1))), dim3(256), 0, st, B, T, s.alpha, s.beta,
@@ -1903,25 +1224,23 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
                           int32_t N, const aa_ref_grads* grads, float* dfeats, void* workspace, size_t workspace_bytes,
                           int32_t flags, aa_stream_t stream, aa_stream_t aux) {
   using namespace aa;
-  int rc = train_check(dims, B, T);
-  if (rc) return rc;
-  if (B == 0 || T == 0 || N == 0) return AA_OK;
-  if (!w || !feats || !tokens || !lengths || !dscores || !grads || !workspace) return AA_ERR_NULL;
-  if (N > B * T || tok_ld < T) return AA_ERR_SHAPE;
-  size_t need;
-  TrainWS s = carve_train(static_cast<char*>(workspace), *dims, B, T, B * T, &need);
-  if (workspace_bytes < need) return AA_ERR_BUFFER;
+  TrainWS s;
+  int rc;
+  if (!train_args({.dims = dims, .B = B, .T = T, .empty = N == 0,
+                   .null = !w || !feats || !tokens || !lengths || !dscores || !grads || !workspace,
+                   .shape = N > B * T || tok_ld < T, .workspace = workspace, .workspace_bytes = workspace_bytes},
+                  &s, &rc))
+    return rc;
   const int H = dims->hidden, E = dims->embed, C = dims->channels, V = dims->vocab, R = T * B, E2 = 2 * E;
   hipStream_t st = (hipStream_t)stream;
   Fork f(st, (hipStream_t)aux);
   const hipStream_t sa = f.aux;
-  const bool bf = (flags & AA_TRAIN_BF16) != 0;
-  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, bf};
-  const GemmCtx ga{sa, s.gsplit2, TR_SPLIT_FLOATS, bf};
+  // gc.bf16: the large GEMMs on k_bgemm, the recurrent steps on k_tr_lstm_b
+  const GemmCtx gc{st, s.gsplit, TR_SPLIT_FLOATS, (flags & AA_TRAIN_BF16) != 0};
+  const GemmCtx ga{sa, s.gsplit2, TR_SPLIT_FLOATS, gc.bf16};
   // AA_TRAIN_SENTINEL_H0: h_{t-1} never entered the gate, so dW_h is the K = 0 product (zeros, as at
   // T = 1) and no gradient flows back into h_{t-1} through it
   const int Rh = (flags & AA_TRAIN_SENTINEL_H0) ? 0 : R - B;
-#define GRAD(f) (grads->f)
   const size_t RH = (size_t)R * H;
   // Streams (Fork): main = dscores -> dU -> attention backward -> sentinel -> LSTM through time ->
   // dx -> embedding / encoder-head gradients; aux = the weight gradients hanging off that chain
@@ -1929,88 +1248,99 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
   // ranking of the embedding gradient.
   f.to_aux();
   // x_t = [embed(tok); v_g] (baseline_attention.py:151-154): the tokens' segmented-sum order
-  AA_TRY(hipMemsetAsync(GRAD(embed_w), 0, sizeof(float) * (size_t)V * E, sa));
+  AA_TRY(hipMemsetAsync(grads->embed_w, 0, sizeof(float) * (size_t)V * E, sa));
   hipLaunchKernelGGL(k_tok_rank, dim3((R + 3) / 4), dim3(256), 0, sa, tokens, tok_ld, B, R, V, s.trank, s.tcount,
                      s.tsmall);
   hipLaunchKernelGGL(k_tok_place, dim3(nblk(R)), dim3(256), 0, sa, R, s.trank, s.tsmall, s.torder);
   hipEvent_t tok_done = f.mark(sa);
   // mlp (adaptive_attention.py:132): dU[prow] = dS W_m; dW_m = dS^T U_p; db_m = colsum(dS)
   const int Vp = (V + 63) / 64 * 64;  // dscores re-pitched to whole 16-B rows for vector loads
-  const bool bg = gc.bf16 && H % 64 == 0;  // the large GEMMs on k_bgemm
   // bf16 steps need dS only as bf16 (the GEMMs) and fp32 for db_m, which colsum reads from dscores
   // itself (same sums, same order): no fp32 re-pitched copy
-  if (bg)  // dS to bf16 for the GEMMs, db_m's column partials on the way (finished below)
+  if (gc.bf16)  // dS to bf16 for the GEMMs, db_m's column partials on the way (finished below)
     hipLaunchKernelGGL(k_pad_rows_colsum, dim3((Vp + 255) / 256, CS_CH), dim3(256), 0, st, dscores, N, V, Vp, s.dspb,
                        s.csum);
   else
     hipLaunchKernelGGL(k_pad_rows, dim3(nblk((int64_t)N * Vp)), dim3(256), 0, st, dscores, N, V, Vp, s.dsp,
                        (__bf16*)nullptr);
-  // dU, dS, dPG, dPS are carved back to back: one clear for the four (nothing below touches dS / dPG
-  // / dPS before the attention backward accumulates into them)
-  AA_TRY(hipMemsetAsync(s.dU, 0, (size_t)((char*)(s.dPS + (size_t)R * PP) - (char*)s.dU), st));
+  // dU, dS, dPG, dPS: one clear for the four (nothing below touches dS / dPG / dPS before the
+  // attention backward accumulates into them)
+  AA_TRY(hipMemsetAsync(s.att_grads.p, 0, s.att_grads.bytes(), st));
   hipLaunchKernelGGL(k_gather_rows, dim3(nblk((int64_t)N * H)), dim3(256), 0, st, s.U, s.prow, N, H, s.Up);
   f.to_aux();  // dW_m on aux
-  if (bg) {
-    const int Kv = Vp, Kn = rup64(N);                                     // dS as bf16 [N][Vp]: k_pad_rows
-    pk_trans(sa, s.dspb, Vp, N, V, s.dspT, Kn);                            // dS^T [V][Kn]
-    pk_trans(sa, s.Up, H, N, H, s.upT, Kn);                                // U_p^T [H][Kn]
-    bgemm(ga, V, H, Kn, s.dspT, Kn, s.upT, Kn, GRAD(mlp_w), H);            // dW_m = dS^T U_p
-    pk_trans(st, w->mlp_w, H, V, H, s.wmT, Kv);                            // W_m^T [H][Kv]
-    bgemm(gc, N, H, Kv, s.dspb, Kv, s.wmT, Kv, s.dU, H, nullptr, s.prow);  // dU[prow] = dS W_m
+  if (gc.bf16) {
+    const int Kv = Vp, Kn = rup64(N);             // dS as bf16 [N][Vp]: k_pad_rows
+    pk_trans(sa, s.dspb, Vp, N, V, s.dspT, Kn);  // dS^T [V][Kn]
+    pk_trans(sa, s.Up, H, N, H, s.upT, Kn);      // U_p^T [H][Kn]
+    bgemm(ga, {.M = V, .N = H, .K = Kn, .A = s.dspT, .lda = Kn, .B = s.upT, .ldb = Kn, .C = grads->mlp_w,
+               .ldc = H});                       // dW_m = dS^T U_p
+    pk_trans(st, w->mlp_w, H, V, H, s.wmT, Kv);  // W_m^T [H][Kv]
+    bgemm(gc, {.M = N, .N = H, .K = Kv, .A = s.dspb, .lda = Kv, .B = s.wmT, .ldb = Kv, .C = s.dU, .ldc = H,
+               .crow = s.prow});                 // dU[prow] = dS W_m
+    colsum_fin(st, s.csum, V, grads->mlp_b);
   } else {
-    tgemm(ga, V, H, N, s.dsp, Vp, 1, s.Up, H, 1, GRAD(mlp_w), H);
-    tgemm(gc, N, H, V, s.dsp, Vp, 0, w->mlp_w, H, 1, s.dU, H, 0, nullptr, nullptr, 0, nullptr, s.prow);
+    tgemm(ga, {.M = V, .N = H, .K = N, .A = s.dsp, .lda = Vp, .at = A_COLS, .W = s.Up, .ldw = H, .wm = W_COLS,
+               .C = grads->mlp_w, .ldc = H});
+    tgemm(gc, {.M = N, .N = H, .K = V, .A = s.dsp, .lda = Vp, .W = w->mlp_w, .ldw = H, .wm = W_COLS, .C = s.dU,
+               .ldc = H, .crow = s.prow});
+    colsum(st, s.dsp, N, V, (int64_t)Vp, s.csum, grads->mlp_b);
   }
-  if (bg) hipLaunchKernelGGL(k_colsum_fin, dim3((V + 255) / 256), dim3(256), 0, st, s.csum, V, GRAD(mlp_b));
-  else colsum(st, s.dsp, N, V, (int64_t)Vp, s.csum, GRAD(mlp_b));
   // Atten backward (adaptive_attention.py:26-58)
   int G, TS;
   atb_groups(B, T, &G, &TS);
-#define AA_ATB(HPT_)                                                                                          \
-  hipLaunchKernelGGL(k_tr_atb_row<HPT_>, dim3(R), dim3(256), 0, st, B, lengths, s.dU, s.alpha, s.beta, s.ctx, s.S, \
-                     s.PG, s.PS, s.VWv, s.V, w->att_affine_h_w, s.dS, s.dPG, s.dPS, s.dz, s.dwr, s.dH);          \
-  hipLaunchKernelGGL(k_tr_atb_img<HPT_>, dim3(B, HPT_ + 1), dim3(256), 0, st, B, TS, G, lengths, s.dU, s.alpha, s.beta, s.PG, \
-                     s.VWv, w->att_affine_h_w, s.dz, s.dwr, s.dV, s.dVWv, s.dwh)
-  switch (H / 256) {
-    case 1: AA_ATB(1); break;
-    case 2: AA_ATB(2); break;
-    case 3: AA_ATB(3); break;
-    default: AA_ATB(4); break;
-  }
-#undef AA_ATB
+  aa_for_hidden(H, [&](auto h) {
+    constexpr int HPT = h.value / 256;
+    hipLaunchKernelGGL(k_tr_atb_row<HPT>, dim3(R), dim3(256), 0, st, B, lengths, s.dU, s.alpha, s.beta, s.ctx, s.S,
+                       s.PG, s.PS, s.VWv, s.V, w->att_affine_h_w, s.dS, s.dPG, s.dPS, s.dz, s.dwr, s.dH);
+    hipLaunchKernelGGL(k_tr_atb_img<HPT>, dim3(B, HPT + 1), dim3(256), 0, st, B, TS, G, lengths, s.dU, s.alpha,
+                       s.beta, s.PG, s.VWv, w->att_affine_h_w, s.dz, s.dwr, s.dV, s.dVWv, s.dwh);
+  });
   // dH = dU (u = c_hat + h) was written by k_tr_atb_row
   f.to_aux();  // the attention's weight gradients and the V side of the encoder on aux
   // (the weights the backward multiplies by untransposed are read from the forward's transposed
   // copies, s.w*T: both operands along K)
-  tgemm(gc, R, H, P, s.dPG, PP, 0, s.wgT, WT_LDP, 0, s.dH, H, 1);                      // dh += dPG W_g
-  tgemm(gc, R, H, P, s.dPS, PP, 0, s.wsT, WT_LDP, 0, s.dS, H, 1);                      // ds += dPS W_s
-  tgemm(ga, P, H, R, s.dPG, PP, 1, s.Hs, H, 1, GRAD(att_affine_g_w), H);                 // dW_g = dPG^T h
-  tgemm(ga, P, H, R, s.dPS, PP, 1, s.S, H, 1, GRAD(att_affine_s_w), H);                  // dW_s = dPS^T s
-  tgemm(ga, B * P, H, P, s.dVWv, PP, 0, s.wvT, WT_LDP, 0, s.dV, H, 1);                 // dV += dVWv W_v
-  tgemm(ga, P, H, B * P, s.dVWv, PP, 1, s.V, H, 1, GRAD(att_affine_v_w), H);             // dW_v = dVWv^T V
-  hipLaunchKernelGGL(k_rowsum_pp, dim3(1), dim3(256), 0, sa, s.dwh, B, GRAD(att_affine_h_w));
+  tgemm(gc, {.M = R, .N = H, .K = P, .A = s.dPG, .lda = PP, .W = s.wgT, .ldw = WT_LDP, .C = s.dH, .ldc = H,
+             .accumulate = true});  // dh += dPG W_g
+  tgemm(gc, {.M = R, .N = H, .K = P, .A = s.dPS, .lda = PP, .W = s.wsT, .ldw = WT_LDP, .C = s.dS, .ldc = H,
+             .accumulate = true});  // ds += dPS W_s
+  tgemm(ga, {.M = P, .N = H, .K = R, .A = s.dPG, .lda = PP, .at = A_COLS, .W = s.Hs, .ldw = H, .wm = W_COLS,
+             .C = grads->att_affine_g_w, .ldc = H});  // dW_g = dPG^T h
+  tgemm(ga, {.M = P, .N = H, .K = R, .A = s.dPS, .lda = PP, .at = A_COLS, .W = s.S, .ldw = H, .wm = W_COLS,
+             .C = grads->att_affine_s_w, .ldc = H});  // dW_s = dPS^T s
+  tgemm(ga, {.M = B * P, .N = H, .K = P, .A = s.dVWv, .lda = PP, .W = s.wvT, .ldw = WT_LDP, .C = s.dV, .ldc = H,
+             .accumulate = true});  // dV += dVWv W_v
+  tgemm(ga, {.M = P, .N = H, .K = B * P, .A = s.dVWv, .lda = PP, .at = A_COLS, .W = s.V, .ldw = H, .wm = W_COLS,
+             .C = grads->att_affine_v_w, .ldc = H});  // dW_v = dVWv^T V
+  hipLaunchKernelGGL(k_rowsum_pp, dim3(1), dim3(256), 0, sa, s.dwh, B, grads->att_affine_h_w);
   // encoder V = relu(A W_a^T + b) (baseline_attention.py:46-51)
   hipLaunchKernelGGL(k_relu_mask, dim3(nblk((int64_t)B * P * H)), dim3(256), 0, sa, s.dV, s.V, (int64_t)B * P * H);
-  if (gc.bf16 && H % 64 == 0) {  // dW_a = dV^T A
+  if (gc.bf16) {  // dW_a = dV^T A
     const int Kb = rup64(B * P);
     pk_trans(sa, s.dV, H, B * P, H, s.dvT, Kb);
     // the feature map's [C][Kb] bf16 operand was packed by the forward (k_pk_feats3, same workspace)
-    bgemm(ga, H, C, Kb, s.dvT, Kb, s.ftC, Kb, GRAD(enc_affine_a_w), C);
+    bgemm(ga, {.M = H, .N = C, .K = Kb, .A = s.dvT, .lda = Kb, .B = s.ftC, .ldb = Kb, .C = grads->enc_affine_a_w,
+               .ldc = C});
   } else {
-    tgemm(ga, H, C, B * P, s.dV, H, 1, feats, C, 2, GRAD(enc_affine_a_w), C);              // dW_a = dV^T A
+    tgemm(ga, {.M = H, .N = C, .K = B * P, .A = s.dV, .lda = H, .at = A_COLS, .W = feats, .ldw = C, .wm = W_NCHW,
+               .C = grads->enc_affine_a_w, .ldc = C});  // dW_a = dV^T A
   }
-  colsum(sa, s.dV, B * P, H, (int64_t)H, s.csum2, GRAD(enc_affine_a_b));
-  if (dfeats) tgemm(ga, B * P, C, H, s.dV, H, 0, w->enc_affine_a_w, C, 1, s.dA, C);      // dA = dV W_a
+  colsum(sa, s.dV, B * P, H, (int64_t)H, s.csum2, grads->enc_affine_a_b);
+  if (dfeats)
+    tgemm(ga, {.M = B * P, .N = C, .K = H, .A = s.dV, .lda = H, .W = w->enc_affine_a_w, .ldw = C, .wm = W_COLS,
+               .C = s.dA, .ldc = C});  // dA = dV W_a
   // Sentinel backward (:79-83): h_{t-1} input = Hs[r - B] for r >= B, 0 for t = 0
   hipLaunchKernelGGL(k_tr_sent_bwd, dim3(nblk((int64_t)RH)), dim3(256), 0, st, s.dS, s.SG, s.Cs, s.dG, s.dC,
                      (int64_t)RH);
   f.to_aux();
-  tgemm(ga, H, E2, R, s.dG, H, 1, s.X, E2, 1, GRAD(sent_affine_x_w), E2);               // dW_x = dG^T x
-  tgemm(ga, H, H, Rh, s.dG + (size_t)B * H, H, 1, s.Hs, H, 1, GRAD(sent_affine_h_w), H);  // dW_h = dG^T h_{t-1}
-  tgemm(gc, R, E2, H, s.dG, H, 0, s.wxT, H, 0, s.dX, E2);                               // dx = dG W_x
-  tgemm(gc, Rh, H, H, s.dG + (size_t)B * H, H, 0, s.whT, H, 0, s.dH, H, 1);             // dh_{t-1} += dG W_h
+  tgemm(ga, {.M = H, .N = E2, .K = R, .A = s.dG, .lda = H, .at = A_COLS, .W = s.X, .ldw = E2, .wm = W_COLS,
+             .C = grads->sent_affine_x_w, .ldc = E2});  // dW_x = dG^T x
+  tgemm(ga, {.M = H, .N = H, .K = Rh, .A = s.dG + (size_t)B * H, .lda = H, .at = A_COLS, .W = s.Hs, .ldw = H,
+             .wm = W_COLS, .C = grads->sent_affine_h_w, .ldc = H});  // dW_h = dG^T h_{t-1}
+  tgemm(gc, {.M = R, .N = E2, .K = H, .A = s.dG, .lda = H, .W = s.wxT, .ldw = H, .C = s.dX, .ldc = E2});  // dx = dG W_x
+  tgemm(gc, {.M = Rh, .N = H, .K = H, .A = s.dG + (size_t)B * H, .lda = H, .W = s.whT, .ldw = H, .C = s.dH, .ldc = H,
+             .accumulate = true});  // dh_{t-1} += dG W_h
   // LSTM backward through time (baseline_attention.py:167-178)
-  AA_TRY(hipMemsetAsync(s.dh_rec, 0, (size_t)((char*)(s.dc_rec + (size_t)B * H) - (char*)s.dh_rec), st));  // adjacent
+  AA_TRY(hipMemsetAsync(s.rec.p, 0, s.rec.bytes(), st));  // dh_rec and dc_rec
   if (gc.bf16) {
     // one fused launch per step (k_tr_lstm_b: dh_rec = DG_{t+1} W_hh, then the cell backward); the
     // gradient into h0 (dh_rec of step 0) is one GEMM after the loop
@@ -2021,18 +1351,18 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
       const float* cp = t ? s.Cs + o - (size_t)B * H : s.c0;
       const float* ga4 = s.GA + (size_t)t * B * 4 * H;
       float* dg = s.DG + (size_t)t * B * 4 * H;
+      // the last step has no later step's DG to multiply: dh_rec = 0, no GEMM
+      const bool last = t == T - 1;
+      const __bf16* dgb_next = last ? nullptr : s.dgb[(t + 1) & 1];
       aa_for_hidden(H, [&](auto h) {
-        if (t == T - 1)
-          hipLaunchKernelGGL((k_tr_lstm_b<h.value, true>), dim3(grid), dim3(256), 0, st, B, (const __bf16*)nullptr,
-                             s.whb, s.dH + o, s.dC + o, s.dc_rec, ga4, s.Cs + o, cp, dg, s.dgb[t & 1]);
-        else
-          hipLaunchKernelGGL((k_tr_lstm_b<h.value, false>), dim3(grid), dim3(256), 0, st, B,
-                             (const __bf16*)s.dgb[(t + 1) & 1], s.whb, s.dH + o, s.dC + o, s.dc_rec, ga4, s.Cs + o, cp,
-                             dg, s.dgb[t & 1]);
+        const auto k = last ? k_tr_lstm_b<h.value, true> : k_tr_lstm_b<h.value, false>;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, B, dgb_next, s.whb, s.dH + o, s.dC + o, s.dc_rec, ga4,
+                           s.Cs + o, cp, dg, s.dgb[t & 1]);
       });
     }
     f.to_aux();  // DG complete: the LSTM weight gradients on aux
-    tgemm(gc, B, H, 4 * H, s.DG, 4 * H, 0, s.whhT, 4 * H, 0, s.dh_rec, H);
+    tgemm(gc, {.M = B, .N = H, .K = 4 * H, .A = s.DG, .lda = 4 * H, .W = s.whhT, .ldw = 4 * H, .C = s.dh_rec,
+               .ldc = H});
   } else {
     int S = 0;  // split count of the pending dh_rec GEMM (0: dh_rec = 0)
     for (int t = T - 1; t >= 0; --t) {
@@ -2042,44 +1372,50 @@ int aa_train_backward_aux(const aa_ref_weights* w, const aa_dims* dims, const fl
                          S > 1 ? gc.split : s.dh_rec, S, s.dc_rec, s.GA + (size_t)t * B * 4 * H, s.Cs + o, cp, B, H,
                          s.DG + (size_t)t * B * 4 * H);
       // dh_{t-1}; the one of step 0 (into h0) is reduced into dh_rec itself
-      S = tgemm(gc, B, H, 4 * H, s.DG + (size_t)t * B * 4 * H, 4 * H, 0, s.whhT, 4 * H, 0, s.dh_rec, H, 0, nullptr,
-                nullptr, 0, nullptr, nullptr, t > 0);
+      const bool defer = t > 0;
+      S = tgemm(gc, {.M = B, .N = H, .K = 4 * H, .A = s.DG + (size_t)t * B * 4 * H, .lda = 4 * H, .W = s.whhT,
+                     .ldw = 4 * H, .C = s.dh_rec, .ldc = H}, defer);
     }
     f.to_aux();
   }
-  tgemm(ga, 4 * H, H, B, s.DG, 4 * H, 1, s.h0, H, 1, GRAD(lstm_w_hh), H);                 // t = 0: h_{-1} = h0
-  tgemm(ga, 4 * H, H, R - B, s.DG + (size_t)B * 4 * H, 4 * H, 1, s.Hs, H, 1, GRAD(lstm_w_hh), H, 1);
-  tgemm(ga, 4 * H, E2, R, s.DG, 4 * H, 1, s.X, E2, 1, GRAD(lstm_w_ih), E2);
-  colsum(sa, s.DG, R, 4 * H, (int64_t)4 * H, s.csum2, GRAD(lstm_b_ih));
-  AA_TRY(hipMemcpyAsync(GRAD(lstm_b_hh), GRAD(lstm_b_ih), sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, sa));
-  tgemm(gc, R, E2, 4 * H, s.DG, 4 * H, 0, s.wihT, 4 * H, 0, s.dX, E2, 1);               // dx += dG W_ih
+  tgemm(ga, {.M = 4 * H, .N = H, .K = B, .A = s.DG, .lda = 4 * H, .at = A_COLS, .W = s.h0, .ldw = H, .wm = W_COLS,
+             .C = grads->lstm_w_hh, .ldc = H});  // t = 0: h_{-1} = h0
+  tgemm(ga, {.M = 4 * H, .N = H, .K = R - B, .A = s.DG + (size_t)B * 4 * H, .lda = 4 * H, .at = A_COLS, .W = s.Hs,
+             .ldw = H, .wm = W_COLS, .C = grads->lstm_w_hh, .ldc = H, .accumulate = true});
+  tgemm(ga, {.M = 4 * H, .N = E2, .K = R, .A = s.DG, .lda = 4 * H, .at = A_COLS, .W = s.X, .ldw = E2, .wm = W_COLS,
+             .C = grads->lstm_w_ih, .ldc = E2});
+  colsum(sa, s.DG, R, 4 * H, (int64_t)4 * H, s.csum2, grads->lstm_b_ih);
+  AA_TRY(hipMemcpyAsync(grads->lstm_b_hh, grads->lstm_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, sa));
+  tgemm(gc, {.M = R, .N = E2, .K = 4 * H, .A = s.DG, .lda = 4 * H, .W = s.wihT, .ldw = 4 * H, .C = s.dX, .ldc = E2,
+             .accumulate = true});  // dx += dG W_ih
   // x_t = [embed(tok); v_g] (baseline_attention.py:151-154)
   f.wait(st, tok_done);
   hipLaunchKernelGGL(k_tr_embed_bwd, dim3(R), dim3(256), 0, st, tokens, tok_ld, B, R, V, s.torder, s.trank, s.tcount,
-                     s.dX, E, GRAD(embed_w));
+                     s.dX, E, grads->embed_w);
   hipLaunchKernelGGL(k_tr_vg_bwd, dim3(nblk((int64_t)B * E)), dim3(256), 0, st, s.dX, s.vg, B, T, E, s.dvg);
   // encoder heads (baseline_attention.py:52-60)
-  tgemm(gc, E, C, B, s.dvg, E, 1, s.a_g, C, 1, GRAD(enc_affine_b_w), C);
-  colsum(st, s.dvg, B, E, (int64_t)E, s.csum, GRAD(enc_affine_b_b));
-  if (s.dc_rec == s.dh_rec + (size_t)B * H && s.c0 == s.h0 + (size_t)B * H) {  // carved back to back: one launch
-    hipLaunchKernelGGL(k_tanh_bwd, dim3(nblk((int64_t)2 * B * H)), dim3(256), 0, st, s.dh_rec, s.h0, (int64_t)2 * B * H);
-  } else {
-    hipLaunchKernelGGL(k_tanh_bwd, dim3(nblk((int64_t)B * H)), dim3(256), 0, st, s.dh_rec, s.h0, (int64_t)B * H);
-    hipLaunchKernelGGL(k_tanh_bwd, dim3(nblk((int64_t)B * H)), dim3(256), 0, st, s.dc_rec, s.c0, (int64_t)B * H);
-  }
-  tgemm(gc, H, C, B, s.dh_rec, H, 1, s.a_g, C, 1, GRAD(enc_affine_h0_w), C);
-  colsum(st, s.dh_rec, B, H, (int64_t)H, s.csum, GRAD(enc_affine_h0_b));
-  tgemm(gc, H, C, B, s.dc_rec, H, 1, s.a_g, C, 1, GRAD(enc_affine_c0_w), C);
-  colsum(st, s.dc_rec, B, H, (int64_t)H, s.csum, GRAD(enc_affine_c0_b));
+  tgemm(gc, {.M = E, .N = C, .K = B, .A = s.dvg, .lda = E, .at = A_COLS, .W = s.a_g, .ldw = C, .wm = W_COLS,
+             .C = grads->enc_affine_b_w, .ldc = C});
+  colsum(st, s.dvg, B, E, (int64_t)E, s.csum, grads->enc_affine_b_b);
+  // h0 = tanh(.), c0 = tanh(.): dh_rec | dc_rec against h0 | c0 in one launch
+  hipLaunchKernelGGL(k_tanh_bwd, dim3(nblk((int64_t)s.rec.n)), dim3(256), 0, st, s.rec.p, s.hc0.p, (int64_t)s.rec.n);
+  tgemm(gc, {.M = H, .N = C, .K = B, .A = s.dh_rec, .lda = H, .at = A_COLS, .W = s.a_g, .ldw = C, .wm = W_COLS,
+             .C = grads->enc_affine_h0_w, .ldc = C});
+  colsum(st, s.dh_rec, B, H, (int64_t)H, s.csum, grads->enc_affine_h0_b);
+  tgemm(gc, {.M = H, .N = C, .K = B, .A = s.dc_rec, .lda = H, .at = A_COLS, .W = s.a_g, .ldw = C, .wm = W_COLS,
+             .C = grads->enc_affine_c0_w, .ldc = C});
+  colsum(st, s.dc_rec, B, H, (int64_t)H, s.csum, grads->enc_affine_c0_b);
   if (dfeats) {  // gradient into the trunk's output A (CNN fine-tuning, train.py:89)
-    tgemm(gc, B, C, E, s.dvg, E, 0, w->enc_affine_b_w, C, 1, s.dag, C);                // d a_g = dv_g W_b
-    tgemm(gc, B, C, H, s.dh_rec, H, 0, w->enc_affine_h0_w, C, 1, s.dag, C, 1);         //   + dh0 W_h0
-    tgemm(gc, B, C, H, s.dc_rec, H, 0, w->enc_affine_c0_w, C, 1, s.dag, C, 1);         //   + dc0 W_c0
+    tgemm(gc, {.M = B, .N = C, .K = E, .A = s.dvg, .lda = E, .W = w->enc_affine_b_w, .ldw = C, .wm = W_COLS,
+               .C = s.dag, .ldc = C});  // d a_g = dv_g W_b
+    tgemm(gc, {.M = B, .N = C, .K = H, .A = s.dh_rec, .lda = H, .W = w->enc_affine_h0_w, .ldw = C, .wm = W_COLS,
+               .C = s.dag, .ldc = C, .accumulate = true});  //   + dh0 W_h0
+    tgemm(gc, {.M = B, .N = C, .K = H, .A = s.dc_rec, .lda = H, .W = w->enc_affine_c0_w, .ldw = C, .wm = W_COLS,
+               .C = s.dag, .ldc = C, .accumulate = true});  //   + dc0 W_c0
   }
   f.to_main();  // everything on aux (dA above) is done before the call's work ends on main
   if (dfeats)
     hipLaunchKernelGGL(k_dfeats, dim3((C + 63) / 64, B), dim3(256), 0, st, s.dA, s.dag, C, dfeats);
   if (f.err) return (int)f.err;
-#undef GRAD
   return aa_launch_status();
 }

@@ -1,5 +1,6 @@
 """The teacher-forced training step (aa_train_forward / aa_train_backward and their _aux forms,
-aa_decoder_forward) at every supported hidden size and at the shape edges of aa_train.hip's host code,
+aa_decoder_forward) at every supported hidden size and at the shape edges of the training step's host
+code (aa_train.hip; the GEMM launches and their split-K decisions in aa_tgemm.hip),
 against a float64 evaluation of the CPU oracle (tests/train_cases.py: the case table, the reference
 and the ReLU kink mask; its conditions are asserted on the CPU in tests/test_train_cases_cpu.py).
 
@@ -40,7 +41,8 @@ measurements only, the bounds are the ones above):
     F      2.0e-3                 4.8e-5     7.6e-3 (encoder.affine_b.bias)           3.4e-2
 
 aa_decoder_forward, max abs: scores 1.2e-6, alpha 3.6e-8, beta 2.5e-8, h 1.0e-7, c 2.4e-7.  No case
-exceeded a bound, on any tensor: the new sizes and shape edges exposed no defect in aa_train.hip.
+exceeded a bound, on any tensor: the new sizes and shape edges exposed no defect in the training
+step (aa_train.hip, aa_tgemm.hip).
 """
 import numpy as np
 import pytest

@@ -121,7 +121,8 @@ def test_case_table(name):
 
 
 def test_case_table_reaches_what_it_claims():
-    """The sizes the table is there for, restated from the host code of aa_train.hip."""
+    """The sizes the table is there for, restated from the host code of aa_train.hip (decoder_core,
+    atb_groups; the GEMMs it launches are aa_tgemm.hip's)."""
     c = tc.CASES
     assert (c["A"].B, c["B"].B, c["C"].B, c["D"].B, c["E"].B, c["F"].B) == (5, 1, 17, 3, 300, 100)
     assert c["C"].lengths == (6, 6, 6, 5, 5, 5, 5, 3, 3, 3, 3, 3, 1, 1, 1, 1, 1)
