@@ -10,7 +10,7 @@ reference's model factory does.
 from .synth import Dims, make_features, make_weights  # noqa: F401
 
 __all__ = ["Dims", "make_features", "make_weights", "Encoder2Decoder", "Config", "DecodePlan", "get_model",
-           "CiderD"]
+           "CiderD", "CaptionMetrics"]
 
 
 def get_model(cf):
@@ -35,6 +35,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch/HIP
     if name == "CiderD":
         from .cider import CiderD
         return CiderD
+    if name == "CaptionMetrics":
+        from .metrics import CaptionMetrics
+        return CaptionMetrics
     if name == "baseline_attention":
         import importlib
         return importlib.import_module(".baseline_attention", __name__)

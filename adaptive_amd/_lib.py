@@ -110,6 +110,13 @@ class CiderCorpus(Structure):
                 ("sigma", c_double)]
 
 
+class MetricsCorpus(Structure):
+    """aa_metrics_corpus: device pointers of the per-image clip counts and the references' tokens."""
+    _fields_ = [("img_ptr", c_void_p), ("clip_ptr", c_void_p), ("clip_keys", c_void_p), ("clip_counts", c_void_p),
+                ("ref_len", c_void_p), ("tok_ptr", c_void_p), ("ref_tok", c_void_p), ("images", c_int32),
+                ("refs", c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/adaptive_amd.h one to one
 SIGNATURES = {
     "aa_abi_version": (c_int, []),
@@ -166,6 +173,9 @@ SIGNATURES = {
     "aa_synth_gumbel": (c_int, [c_void_p, c_int64, c_uint64, c_int64, c_void_p]),
     "aa_cider_score": (c_int, [POINTER(CiderCorpus), c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                                c_void_p]),
+    "aa_metrics_score": (c_int, [POINTER(MetricsCorpus), c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aa_bleu_corpus": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     "aa_vocab_logits": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_void_p]),
     "aa_vocab_logits_at": (c_int, [POINTER(Model), c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "aa_cross_entropy_workspace_bytes": (c_size_t, [c_int32]),

@@ -90,6 +90,7 @@ class _Flat:
             bad = tok[(tok < 0) | (tok >= TOKEN_LIMIT)][0]
             raise ValueError(f"{what}: token {int(bad)} outside [0, {TOKEN_LIMIT})")
         self.length = length                                  # tokens per caption
+        self.tok = tok                                        # the cut captions' tokens, caption after caption
         self.cap_image = np.repeat(np.arange(self.images), per_image)
         self.caps = ncap
         # every n-gram of every caption as (caption, key); a caption's tokens are contiguous in tok

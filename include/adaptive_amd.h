@@ -600,6 +600,60 @@ AA_API int aa_cider_score(const aa_cider_corpus* corpus, const int64_t* ids, int
                           int64_t ids_ld, int32_t end_id, const int32_t* image, double* scores,
                           aa_stream_t stream);
 
+/* ---- BLEU-1..4 and ROUGE-L of token-id captions (the rest of coco_eval's table that ids can give) ---
+ * The reference's coco/pycocoevalcap/bleu/bleu_scorer.py as bleu/bleu.py calls it (option 'closest',
+ * n = 4) and rouge/rouge.py, on token ids in place of words; restated on the CPU by
+ * tests/metrics_oracle.py.  A caption is cut as for aa_cider_score.  For a hypothesis of L tokens
+ * against the references of its image:
+ *   testlen   = L;   guess_n = max(0, L - n + 1), n = 1..4
+ *   correct_n = sum over the distinct n-grams g of order n of min(c_hyp(g), max_refs c_ref(g))
+ *   reflen    = the reference length l with the smallest (|l - L|, l): a tie goes to the shorter
+ *   sentence BLEU: b = 1; for n = 1..4: b *= (correct_n + 1e-15) / (guess_n + 1e-9),
+ *               bleu_n = pow(b, 1 / n); ratio = (L + 1e-15) / (reflen + 1e-9); if ratio < 1 every
+ *               bleu_n *= exp(1 - 1 / ratio)
+ *   corpus BLEU: the same expression on the integer totals of the ten statistics over the rows
+ *   ROUGE-L, beta = 1.2: per reference prec = lcs / max(L, 1), rec = lcs / max(Lr, 1), lcs the longest
+ *               common subsequence -- 0 when exactly one side is empty and 1 WHEN BOTH ARE (the
+ *               reference splits "" into one empty word; reproduced, not corrected); P = max prec,
+ *               Rc = max rec, each over the references on its own;
+ *               score = (1 + beta^2) P Rc / (Rc + beta^2 P) if both are non-zero, else 0
+ * All float arithmetic is float64 without contraction; the statistics are integers, so a row's outputs
+ * are bit-reproducible and depend on no other row.
+ * aa_metrics_corpus: a host struct of device pointers, built once per corpus
+ *   (adaptive_amd.metrics.CaptionMetrics).  Image i owns references img_ptr[i] .. img_ptr[i + 1] - 1 and
+ *   the clip-count entries clip_ptr[i] .. clip_ptr[i + 1] - 1: clip_keys (aa_cider_score's n-gram keys,
+ *   ascending within an image) and clip_counts (the largest count of the n-gram in one reference of
+ *   the image).  Reference r has ref_len[r] tokens, ref_tok[tok_ptr[r] ..]; references may be empty
+ *   and may be longer than AA_CIDER_MAX_T.
+ * aa_metrics_score: row r of ids [R, T] (int64, row pitch ids_ld) against image image[r] (NULL: image
+ *   r).  stats [R][10] int32 = correct_1..4, guess_1..4, testlen, reflen; bleu [R][4] and rouge [R]
+ *   float64.  One launch, no workspace, no synchronisation.  A token outside [0, 65535) before the
+ *   row's first end_id, or an image outside [0, images), makes that row's bleu and rouge NaN and its
+ *   statistics 0 (so it adds nothing to a corpus total); no other row is affected.  Every loop over
+ *   the corpus's data is bounded (the search by 64 halvings, the LCS by the reference's stored
+ *   length, the references by the corpus's count); the CSR offsets themselves are trusted.
+ * aa_bleu_corpus: out [4] float64 = corpus BLEU-1..4 of stats [R][10] (int64 column totals, then the
+ *   expression above).  One launch of one workgroup.
+ * Checks: aa_metrics_score as aa_cider_score -- AA_ERR_SHAPE for R < 0, T outside [0, AA_CIDER_MAX_T]
+ *   or ids_ld < T; R == 0 returns AA_OK before any pointer is looked at; then AA_ERR_NULL for a NULL
+ *   corpus, AA_ERR_SHAPE for images < 1 or refs < 1, AA_ERR_NULL for a NULL corpus array, output, or
+ *   ids (ids may be NULL when T == 0).  aa_bleu_corpus: AA_ERR_SHAPE for R < 0; R == 0 returns AA_OK
+ *   and writes nothing; AA_ERR_NULL for a NULL stats or out. */
+typedef struct aa_metrics_corpus {
+  const int32_t* img_ptr;      /* [images + 1] */
+  const int32_t* clip_ptr;     /* [images + 1] */
+  const uint64_t* clip_keys;   /* [clip_ptr[images]], ascending within an image */
+  const int32_t* clip_counts;  /* [clip_ptr[images]] */
+  const int32_t* ref_len;      /* [refs]: tokens */
+  const int32_t* tok_ptr;      /* [refs + 1] */
+  const uint16_t* ref_tok;     /* [tok_ptr[refs]] */
+  int32_t images, refs;
+} aa_metrics_corpus;
+AA_API int aa_metrics_score(const aa_metrics_corpus* corpus, const int64_t* ids, int32_t R, int32_t T,
+                            int64_t ids_ld, int32_t end_id, const int32_t* image, int32_t* stats, double* bleu,
+                            double* rouge, aa_stream_t stream);
+AA_API int aa_bleu_corpus(const int32_t* stats, int32_t R, double* out, aa_stream_t stream);
+
 /* Measurement helper (bench.py's roofline block; not on the decode path): one streaming read of
  * nbytes (multiple of 16, 16-B aligned) from src by `blocks` workgroups, each writing its partial sum
  * to out[block].  Timed over a buffer resident in the 256 MiB Infinity Cache it gives the MALL-served
