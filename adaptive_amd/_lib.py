@@ -26,6 +26,13 @@ DECODE_SPLIT_RESCORE = 1024  # rescoring in its own launch per step (cross-check
 DECODE_RS_SELF = 2048  # test hook: fused launch's LSTM workgroups rescore unpublished rows themselves
 DECODE_SCREEN4 = 4096  # vocab screen on k_vscreen2 (4 waves) instead of k_vscreen8: the same summaries
 DECODE_BASELINE = 8192  # baseline (no-sentinel) model: must match how the model was packed
+DECODE_ENC_BF16X3 = 16384  # test hook: k_enc_v4 on its bf16x3 body (six products) in every workgroup
+# k_enc_v4's fp16x2 fast path (aa_internal.hpp ENC_F16_*): feature scale 2^A_EXP, range-guard threshold,
+# W_a scaled so that max|W_a| 2^e lies in [2^W_TOP, 2^(W_TOP + 1)), |e| <= W_ECLAMP
+ENC_F16_A_EXP = 6
+ENC_F16_A_MAX = 512.0
+ENC_F16_W_TOP = 13
+ENC_F16_W_ECLAMP = 64
 BEAM_FAST = 256
 TRAIN_BF16 = 128
 TRAIN_SENTINEL_H0 = 64  # the sentinel gate without its h_{t-1} term, as the one-token decode step

@@ -694,7 +694,8 @@ class Encoder2Decoder(nn.Module):
         with torch.cuda.device(dev):
             rc = lib.aa_encoder_tail(model, images.data_ptr(), B, a_g.data_ptr(), V.data_ptr(), v_g.data_ptr(),
                                      h0.data_ptr(), c0.data_ptr(), VWv.data_ptr(),
-                                     _lib.DECODE_FP32_ENCODER if self.fp32_encoder else 0, _lib.stream_handle())
+                                     self._decode_flags() & (_lib.DECODE_FP32_ENCODER | _lib.DECODE_ENC_BF16X3),
+                                     _lib.stream_handle())
         _lib.check(rc, "encoder_tail")
         return V, v_g, (h0, c0), a_g, VWv
 

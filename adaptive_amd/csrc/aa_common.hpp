@@ -41,6 +41,7 @@ constexpr int P = 49;          // attention width == 7x7 spatial locations (adap
 constexpr int PP = 64;         // padded attention width (VWv row pitch, W_v rows)
 constexpr int MAX_H = 1024;    // kernels keep h / s / u rows in LDS
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // accurate libm (expf / tanhf from the device library, no fast-math)

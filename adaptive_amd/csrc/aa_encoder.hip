@@ -5,9 +5,10 @@
 //     k_gemm_bias     table[v] = embed[v] . [W_ih(emb part); W_x(emb part)]^T   (V x 5H)
 //     k_pack_mlp      bf16 copy and row norms of W_m for the vocab screen (k_pack_gs: per granule)
 //     k_pack_w3 / w4  bf16x3 MFMA-fragment copies of W_a, W_hh, W_m, the heads, W_vg, W_v
+//     k_w4h_scale, k_pack_w4h  the scaled fp16x2 fragment copy of W_a (k_enc_v4's fast path)
 //   encoder tail (once per batch), encoder_launch
 //     k_enc_v4        V = relu(A^T W_a^T + b_a) [B*49, H] and a_g = AvgPool2d(7)(A) in one pass over the
-//                     feature map                                    baseline_attention.py:46-51
+//                     feature map (fp16x2 split, bf16x3 fallback)    baseline_attention.py:46-51
 //     k_gemm3         v_g | h0 | c0 = act(a_g [W_b;W_h0;W_c0]^T + b) (MODE_HEADS)              :53-60
 //                     VWv = V W_v^T (step-invariant, hoisted)         adaptive_attention.py:34
 //                     xg = v_g . [W_ih(v_g part); W_x(v_g part)]^T + b_ih + b_hh (step-invariant)
@@ -257,17 +258,58 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 // each; what H = 512 launches): k_enc_v4 247 -> 242 us, sequential decode +0.9 % (A/B, two rounds)
 constexpr int ENC4_NW = 16;
 
+// The fast path (default): the same GEMM from a TWO-way fp16 split, three products per block instead
+// of six.  fp16 has an 11-bit significand, so x ~ hi + lo (hi = fp16(x), lo = fp16(x - hi), the
+// difference exact in fp32) carries 22 bits: lo's own rounding leaves <= 2^-22 |x| while lo is a
+// normal fp16 number.  hi.W_hi, hi.W_lo and lo.W_hi are exact in the fp32 accumulator (22-bit
+// products); the dropped lo.W_lo is <= 2^-22 |a w|.  Per term that is <= 3 x 2^-22 |a w| in the worst
+// case and ~2^-24 |a w| rms, so over K = 2048 terms of independent sign the result stays in the
+// fp32-GEMM class (fp32 accumulation, the same in both paths, dominates).
+// fp16's range is what needs care (bf16 has fp32's):
+//   W_a is scaled at pack time by one power of two per tensor (k_pack_w4h: max|W_a| 2^e lands in
+//   [2^13, 2^14), a factor >= 4 under fp16's 65504), so the lo part of every weight down to
+//   2^-17 max|W_a| is a normal fp16 number;
+//   the features are scaled by 2^ENC_F16_A_EXP = 64 as they are split.  A larger scale keeps the lo
+//   parts of smaller features normal, a smaller one raises the overflow threshold; they multiply to
+//   2^15.  Post-ReLU trunk features are O(1) with maxima of a few tens, so the threshold
+//   ENC_F16_A_MAX = 512 sits an order of magnitude above them (hi <= 2^15, a factor 2 under 65504),
+//   and a feature keeps a normal lo part down to 2^-3 / 64 = 2^-9.  Below that lo is subnormal: its
+//   error is 2^-25 absolute (of the scaled value; MFMA reads fp16 subnormals as they are), i.e.
+//   2^-31 per feature: 2^-22 of a 2^-9 feature, 2^-20 of the 2^-11 mean of features spread over
+//   [1e-6, 1e-3].  A map whose features are ALL that small still meets the scheme's 2^-21 of
+//   sum |a w|, because the errors are independent in sign over K = 2048 terms (emulation: 2^-24;
+//   on the device, U[0,1) x 1e-4 features: 5.3e-7 against bf16x3's 1.6e-7, x 1 and x 100: 1.7e-7
+//   against 2.4e-7, tests/test_gpu_encoder_f16.py) -- small features cost accuracy gradually, they
+//   never trip anything.
+//   Both scales are exact powers of two, removed by one exact multiply before bias and relu.
+// Range guard: every staging thread notes a feature that is not finite or not below ENC_F16_A_MAX
+// in magnitude; after the K loop a workgroup that saw one (an LDS flag: no global state, no second
+// launch, no host sync) recomputes its two images with the bf16x3 body below, so such an image comes
+// out bit for bit as the bf16x3 kernel computes it.  The bf16x3 body needs the larger register set,
+// so carrying it costs the fast path nothing.  x3_only (AA_DECODE_ENC_BF16X3) sends every workgroup
+// through the bf16x3 body only.  a_g is computed from the fp32 stage copy either way: bit-identical.
+template <bool F>
+struct BoolC {
+  static constexpr bool value = F;
+};
+// (Tried on the fast path: stage s + 1's W fragments in a second register set, loaded at the start of
+// stage s instead of after the pair's last MFMA -- 16 + 16 VGPRs of W.  128 VGPRs and 20 B/lane of
+// scratch at 16 waves, k_enc_v4 175.7 / 178.9 -> 182.1 / 182.6 us in A/B: not kept.  The W loads'
+// latency is not what the stage waits for.)
+
 template <int NCB, int NW = 8>
 __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ feats, int B, int C,
-                                                const bf16x8* __restrict__ W4, const float* __restrict__ bias,
-                                                float* __restrict__ V, float* __restrict__ a_g) {
+                                                const bf16x8* __restrict__ W4, const f16x8* __restrict__ W4h,
+                                                const float* __restrict__ w4h_sc, const float* __restrict__ bias,
+                                                float* __restrict__ V, float* __restrict__ a_g, int x3_only) {
   static_assert(NCB % 2 == 0, "columns are processed in pairs of 16-column blocks");
-  constexpr int H = 16 * NCB * NW, NPAIR = NCB / 2, PL = E4_RB * 16 * E4_LD;  // PL: one plane, bf16
+  constexpr int H = 16 * NCB * NW, NPAIR = NCB / 2, PL = E4_RB * 16 * E4_LD;  // PL: one plane, 16-bit elements
   constexpr int NT = 64 * NW;
   const bool stager = NW == 8 || threadIdx.x < 512;
-  __shared__ __attribute__((aligned(16))) __bf16 As[2][3][PL];
+  __shared__ __attribute__((aligned(16))) __bf16 As[2][3][PL];  // (the fp16 path: planes 0, 1 hold fp16 bits)
   __shared__ __attribute__((aligned(16))) float Sg[2][2 * 32 * E4_SP];  // fp32 stage copy for a_g
   __shared__ __attribute__((aligned(16))) float Ag[2 * E4_MAXC];        // a_g of the two images
+  __shared__ int over_any;                                              // the range guard's flag
   const int M = B * P, KC = C / 32;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int m0 = blockIdx.x * E4_ROWS;
@@ -286,106 +328,154 @@ __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ fe
   const int so = sr * E4_LD + 8 * kg;
   // fragment reads: lane l -> row 16 rb + (l & 15), k = 8 (l >> 4)
   const int fo = (lane & 15) * E4_LD + 8 * (lane >> 4);
-  const bf16x8* wsrc = W4 + (size_t)(wave * NCB) * KC * 3 * 64 + lane;  // block nb = wave NCB + c
-  float ra[8];
-  bf16x8 wv[NCB][3];
   floatx4 acc[E4_RB][NCB];
-#pragma unroll
-  for (int rb = 0; rb < E4_RB; ++rb)
-#pragma unroll
-    for (int c = 0; c < NCB; ++c) acc[rb][c] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-  auto gload_a = [&](int s) {
-    const float* src = arow + (int64_t)(32 * s) * P;
+  // The K loop, as the fp16x2 fast path (F16) or the bf16x3 body: NPL planes of A in LDS and of W in
+  // registers (16-byte fragments either way; the fp16 ones travel as bf16x8 bits).  Returns whether
+  // this thread staged a feature outside the fast path's range (F16 only).
+  auto kloop = [&](auto f16) -> bool {
+    constexpr bool F16 = decltype(f16)::value;
+    constexpr int NPL = F16 ? 2 : 3;
+    const bf16x8* wsrc = (F16 ? reinterpret_cast<const bf16x8*>(W4h) : W4) + (size_t)(wave * NCB) * KC * NPL * 64 +
+                         lane;  // block nb = wave NCB + c
+    float ra[8];
+    bf16x8 wv[NCB][NPL];
+    bool over = false;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ra[i] = __builtin_nontemporal_load(src + i * P);
-  };
-  auto gload_w = [&](int s, int c) {
+    for (int rb = 0; rb < E4_RB; ++rb)
 #pragma unroll
-    for (int q = 0; q < 3; ++q) wv[c][q] = wsrc[((size_t)c * KC * 3 + (size_t)s * 3 + q) * 64];
-  };
-  auto lstore_a = [&](int buf) {
-    bf16x8 x[3];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      __bf16 x0, x1, x2;
-      split3(ra[i], x0, x1, x2);
-      x[0][i] = x0; x[1][i] = x1; x[2][i] = x2;
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(&As[buf][q][so]) = x[q];
-    if (t < 4 * E4_ROWS) {  // sr = 49 image + p
-      const int img = sr >= P, pp = sr - img * P;
-      float* g = &Sg[buf][(img * 32 + 8 * kg) * E4_SP + pp];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g[i * E4_SP] = ra[i];
-    }
-  };
+      for (int c = 0; c < NCB; ++c) acc[rb][c] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-  const int ns = KC;
-  if (stg) gload_a(0);
+    auto gload_a = [&](int s) {
+      const float* src = arow + (int64_t)(32 * s) * P;
 #pragma unroll
-  for (int c = 0; c < NCB; ++c) gload_w(0, c);
-  if (stg) lstore_a(0);
-  if (stg) gload_a(ns > 1 ? 1 : 0);
-  __syncthreads();
-  for (int s = 0; s < ns; ++s) {
-    const int buf = s & 1, s1 = s + 1 < ns ? s + 1 : ns - 1, s2 = s + 2 < ns ? s + 2 : ns - 1;
-    // A of stage s+1 (in ra) into the other buffer: its last readers (stage s-1) passed the barrier
-    if (stg) {
-      lstore_a(buf ^ 1);
-      gload_a(s2);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const __bf16* Ab = &As[buf][0][fo];
+      for (int i = 0; i < 8; ++i) ra[i] = __builtin_nontemporal_load(src + i * P);
+    };
+    auto gload_w = [&](int s, int c) {
 #pragma unroll
-    for (int cp = 0; cp < NPAIR; ++cp) {
+      for (int q = 0; q < NPL; ++q) wv[c][q] = wsrc[((size_t)c * KC * NPL + (size_t)s * NPL + q) * 64];
+    };
+    auto lstore_a = [&](int buf) {
+      if constexpr (F16) {
+        f16x8 x[2];
 #pragma unroll
-      for (int rb = 0; rb < E4_RB; ++rb) {
-        bf16x8 fa[3];
+        for (int i = 0; i < 8; ++i) {
+          _Float16 hi, lo;
+          split2h(ra[i] * (float)(1 << ENC_F16_A_EXP), hi, lo);
+          x[0][i] = hi; x[1][i] = lo;
+          over |= !(__builtin_fabsf(ra[i]) < ENC_F16_A_MAX);  // also true for NaN
+        }
 #pragma unroll
-        for (int q = 0; q < 3; ++q) fa[q] = *reinterpret_cast<const bf16x8*>(Ab + q * PL + rb * 16 * E4_LD);
-        // the pair's two accumulator chains interleaved (each chain's product order unchanged:
-        // bit-identical), so no MFMA waits on its immediate predecessor
-        {
+        for (int q = 0; q < 2; ++q) *reinterpret_cast<bf16x8*>(&As[buf][q][so]) = __builtin_bit_cast(bf16x8, x[q]);
+      } else {
+        bf16x8 x[3];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          __bf16 x0, x1, x2;
+          split3(ra[i], x0, x1, x2);
+          x[0][i] = x0; x[1][i] = x1; x[2][i] = x2;
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(&As[buf][q][so]) = x[q];
+      }
+      if (t < 4 * E4_ROWS) {  // sr = 49 image + p
+        const int img = sr >= P, pp = sr - img * P;
+        float* g = &Sg[buf][(img * 32 + 8 * kg) * E4_SP + pp];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g[i * E4_SP] = ra[i];
+      }
+    };
+
+    const int ns = KC;
+    if (stg) gload_a(0);
+#pragma unroll
+    for (int c = 0; c < NCB; ++c) gload_w(0, c);
+    if (stg) lstore_a(0);
+    if (stg) gload_a(ns > 1 ? 1 : 0);
+    __syncthreads();
+    for (int s = 0; s < ns; ++s) {
+      const int buf = s & 1, s1 = s + 1 < ns ? s + 1 : ns - 1, s2 = s + 2 < ns ? s + 2 : ns - 1;
+      // A of stage s+1 (in ra) into the other buffer: its last readers (stage s-1) passed the barrier
+      if (stg) {
+        lstore_a(buf ^ 1);
+        gload_a(s2);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const __bf16* Ab = &As[buf][0][fo];
+#pragma unroll
+      for (int cp = 0; cp < NPAIR; ++cp) {
+#pragma unroll
+        for (int rb = 0; rb < E4_RB; ++rb) {
+          bf16x8 fa[NPL];
+#pragma unroll
+          for (int q = 0; q < NPL; ++q) fa[q] = *reinterpret_cast<const bf16x8*>(Ab + q * PL + rb * 16 * E4_LD);
+          // the pair's two accumulator chains interleaved (each chain's product order unchanged:
+          // bit-identical), so no MFMA waits on its immediate predecessor
           const int c0 = 2 * cp, c1 = c0 + 1;
           floatx4 x = acc[rb][c0], y = acc[rb][c1];
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[c0][0], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[c1][0], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c0][1], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c1][1], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][2], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][2], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c0][0], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c1][0], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][1], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][1], y, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][0], x, 0, 0, 0);
-          y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][0], y, 0, 0, 0);
+          if constexpr (F16) {  // smallest first: lo.W_hi, hi.W_lo, hi.W_hi
+            const f16x8 ah = __builtin_bit_cast(f16x8, fa[0]), al = __builtin_bit_cast(f16x8, fa[1]);
+            const f16x8 w0h = __builtin_bit_cast(f16x8, wv[c0][0]), w0l = __builtin_bit_cast(f16x8, wv[c0][1]);
+            const f16x8 w1h = __builtin_bit_cast(f16x8, wv[c1][0]), w1l = __builtin_bit_cast(f16x8, wv[c1][1]);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, w0h, x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, w1h, y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, w0l, x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, w1l, y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, w0h, x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, w1h, y, 0, 0, 0);
+          } else {
+            x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[c0][0], x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wv[c1][0], y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c0][1], x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c1][1], y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][2], x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][2], y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c0][0], x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wv[c1][0], y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][1], x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][1], y, 0, 0, 0);
+            x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c0][0], x, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wv[c1][0], y, 0, 0, 0);
+          }
           acc[rb][c0] = x;
           acc[rb][c1] = y;
         }
+        gload_w(s1, 2 * cp);
+        gload_w(s1, 2 * cp + 1);
+        // re-read the A fragments for the next pair instead of keeping them all live (VGPR budget)
+        asm volatile("" ::: "memory");
       }
-      gload_w(s1, 2 * cp);
-      gload_w(s1, 2 * cp + 1);
-      // re-read the A fragments for the next pair instead of keeping all 21 live (VGPR budget)
-      asm volatile("" ::: "memory");
-    }
-    // one wave per stage (rotating over waves 0..7) sums the stage's channels for a_g (giving the turns
-    // to waves 8..15, which do no A staging, measured 4 us slower at NW = 16)
-    if (wave == (s & 7)) {  // lane -> (image lane / 32, channel lane % 32)
-      const float* g = &Sg[buf][lane * E4_SP];
-      float sum = 0.f;
+      // one wave per stage (rotating over waves 0..7) sums the stage's channels for a_g (giving the turns
+      // to waves 8..15, which do no A staging, measured 4 us slower at NW = 16)
+      if (wave == (s & 7)) {  // lane -> (image lane / 32, channel lane % 32)
+        const float* g = &Sg[buf][lane * E4_SP];
+        float sum = 0.f;
 #pragma unroll 4
-      for (int pp = 0; pp < 48; pp += 4) {  // 16-B reads (E4_SP * 4 B = 13 x 16 B), summed in p order
-        const float4 v = *reinterpret_cast<const float4*>(g + pp);
-        sum += v.x; sum += v.y; sum += v.z; sum += v.w;
+        for (int pp = 0; pp < 48; pp += 4) {  // 16-B reads (E4_SP * 4 B = 13 x 16 B), summed in p order
+          const float4 v = *reinterpret_cast<const float4*>(g + pp);
+          sum += v.x; sum += v.y; sum += v.z; sum += v.w;
+        }
+        sum += g[48];
+        Ag[(lane >> 5) * C + 32 * s + (lane & 31)] = sum / 49.0f;
       }
-      sum += g[48];
-      Ag[(lane >> 5) * C + 32 * s + (lane & 31)] = sum / 49.0f;
+      __syncthreads();
+      __builtin_amdgcn_sched_barrier(0);
     }
+    return over;
+  };
+
+  bool x3 = x3_only != 0;  // (workgroup-uniform)
+  float unscale = 1.0f;
+  if (!x3) {
+    if (t == 0) over_any = 0;  // (ordered before the flag's writers by the K loop's barriers)
+    if (kloop(BoolC<true>{})) over_any = 1;
     __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
+    x3 = over_any != 0;
+    unscale = w4h_sc[0];
+  }
+  if (x3) {  // every LDS read of the fast path's last stage is behind its closing barrier
+    kloop(BoolC<false>{});
+    unscale = 1.0f;  // (x 1.0f is exact: the bf16x3 body's V is what it was without the fast path)
   }
   // a_g of the workgroup's images (the last workgroup of an odd batch holds one)
   for (int i = t; i < 2 * C; i += NT) {
@@ -410,7 +500,8 @@ __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ fe
     for (int c = 0; c < NCB; ++c) {
       const int col = (wave * NCB + c) * 16 + (lane & 15);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) Vs[(4 * (lane >> 4) + i) * VSP + col] = reluf_(acc[rb][c][i] + bvs[c]);
+      for (int i = 0; i < 4; ++i)
+        Vs[(4 * (lane >> 4) + i) * VSP + col] = reluf_(acc[rb][c][i] * unscale + bvs[c]);  // the exact un-scale first
     }
     __syncthreads();
     constexpr int F4 = 16 * H / 4;  // float4s of the block
@@ -689,6 +780,49 @@ __global__ void k_pack_w4(const float* __restrict__ w, int C, bf16x8* __restrict
   o[128] = lo;
 }
 
+// The fp16x2 copy of W_a (k_enc_v4's fast path).  k_w4h_scale (one workgroup): the tensor's power-of-two
+// scale from max|W_a| (see ENC_F16_W_TOP), stored with the model as sc[0] = 2^-(e + ENC_F16_A_EXP), the
+// kernel's un-scale, and sc[1] = e.  k_pack_w4h: W_a 2^e split in two fp16 planes (hi, lo) in k_pack_w4's
+// fragment order, planes at out[((nb KC + kc) 2 + q) 64 + l].
+__global__ __launch_bounds__(1024) void k_w4h_scale(const float* __restrict__ w, size_t n, float* __restrict__ sc) {
+  __shared__ uint32_t part[16];
+  uint32_t mx = 0;  // max |w| by its bit pattern (a NaN or inf ends up on top and gives e = 0)
+  for (size_t i = threadIdx.x; i < n; i += 1024) {
+    const uint32_t u = __float_as_uint(w[i]) & 0x7FFFFFFFu;
+    mx = u > mx ? u : mx;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t x = (uint32_t)__shfl_xor((int)mx, o, 64);
+    mx = x > mx ? x : mx;
+  }
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 16; ++i) mx = part[i] > mx ? part[i] : mx;
+    const int be = (int)(mx >> 23);  // biased exponent: 0 (zero / subnormal) and 255 (inf / NaN) take e = 0
+    int e = be == 0 || be == 255 ? 0 : ENC_F16_W_TOP - (be - 127);
+    e = e > ENC_F16_W_ECLAMP ? ENC_F16_W_ECLAMP : e < -ENC_F16_W_ECLAMP ? -ENC_F16_W_ECLAMP : e;
+    sc[0] = ldexpf(1.0f, -(e + ENC_F16_A_EXP));
+    sc[1] = (float)e;
+  }
+}
+__global__ void k_pack_w4h(const float* __restrict__ w, int C, const float* __restrict__ sc, f16x8* __restrict__ out) {
+  const int KC = C / 32, nb = blockIdx.x / KC, kc = blockIdx.x % KC, l = threadIdx.x;
+  const float* src = w + (int64_t)(16 * nb + (l & 15)) * C + 32 * kc + 8 * (l >> 4);
+  const float scale = ldexpf(1.0f, (int)sc[1]);
+  f16x8 h, lo;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    _Float16 a, b;
+    split2h(src[j] * scale, a, b);
+    h[j] = a; lo[j] = b;
+  }
+  f16x8* o = out + ((size_t)blockIdx.x * 2) * 64 + l;
+  o[0] = h;
+  o[64] = lo;
+}
+
 // wgs[tile][j][u] = (j < 49 ? W_g[j] : W_s[j - 49])[tile*16 + u]
 __global__ void k_pack_wgs(const float* __restrict__ wg, const float* __restrict__ ws, int H, float* __restrict__ out) {
   const int tile = blockIdx.x;
@@ -808,6 +942,9 @@ int aa_pack_weights(const aa_model* m, const aa_ref_weights* w, aa_stream_t stre
                      reinterpret_cast<bf16x8*>(base + L.mlp_w3));
   hipLaunchKernelGGL(k_pack_w4, dim3((H / 16) * (C / 32)), dim3(64), 0, s, w->enc_affine_a_w, C,
                      reinterpret_cast<bf16x8*>(base + L.enc_w4));
+  hipLaunchKernelGGL(k_w4h_scale, dim3(1), dim3(1024), 0, s, w->enc_affine_a_w, (size_t)H * C, base + L.enc_w4h_sc);
+  hipLaunchKernelGGL(k_pack_w4h, dim3((H / 16) * (C / 32)), dim3(64), 0, s, w->enc_affine_a_w, C,
+                     (const float*)(base + L.enc_w4h_sc), reinterpret_cast<f16x8*>(base + L.enc_w4h));
   hipLaunchKernelGGL(k_pack_w4, dim3((L.NHp / 16) * (C / 32)), dim3(64), 0, s, base + L.heads_w, C,
                      reinterpret_cast<bf16x8*>(base + L.heads_w4));
   if (E % 32 == 0)
@@ -894,12 +1031,14 @@ int aa::encoder_launch(const Layout& L, const MP& p, const float* feats, int B, 
     // k_enc_v4 computes V and a_g in one pass over the feature map; the a_g branch (heads, x_g)
     // then runs on aux beside the VWv GEMM.  (Trace: the fused avg-pool is a zero-length pair.)
     const int nwg = (B * P + E4_ROWS - 1) / E4_ROWS;
+    const int x3_only = (flags & AA_DECODE_ENC_BF16X3) != 0;
     if (H == 512)
       AA_TLAUNCH(ev, 2, (k_enc_v4<32 / ENC4_NW, ENC4_NW>), dim3(nwg), dim3(64 * ENC4_NW), 0, s, feats, B, C,
-                 (const bf16x8*)p.enc_w4, (const float*)p.enc_a_b, V, a_g);
+                 (const bf16x8*)p.enc_w4, (const f16x8*)p.enc_w4h, (const float*)p.enc_w4h_sc, (const float*)p.enc_a_b,
+                 V, a_g, x3_only);
     else
       AA_TLAUNCH(ev, 2, k_enc_v4<2>, dim3(nwg), dim3(512), 0, s, feats, B, C, (const bf16x8*)p.enc_w4,
-                 (const float*)p.enc_a_b, V, a_g);
+                 (const f16x8*)p.enc_w4h, (const float*)p.enc_w4h_sc, (const float*)p.enc_a_b, V, a_g, x3_only);
     if (sa != s) {  // aux waits for a_g
       hipEvent_t agr = nullptr;
       AA_TRY(hipEventCreateWithFlags(&agr, hipEventDisableTiming));

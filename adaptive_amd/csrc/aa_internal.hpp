@@ -52,7 +52,7 @@ struct Layout {
   int NH, NHp;   // heads rows E + 2H, padded to 64
   int Vp;        // vocab rows padded to 128
   int N5;        // 5H: 4 gates (packed tile order) + sentinel
-  size_t enc_a_w, enc_a_b, enc_w3, whh3, heads_w, heads_b, wv, wg, ws, wh, whh, wemb, wvg, bias5, table, mlp_w, mlp_b, mlp_wb, mlp_wn, mlp_gs, wgs, mlp_w3, enc_w4, heads_w4, wvg4, wv4;
+  size_t enc_a_w, enc_a_b, enc_w3, whh3, heads_w, heads_b, wv, wg, ws, wh, whh, wemb, wvg, bias5, table, mlp_w, mlp_b, mlp_wb, mlp_wn, mlp_gs, wgs, mlp_w3, enc_w4, heads_w4, wvg4, wv4, enc_w4h, enc_w4h_sc;
   size_t total_floats;
 };
 
@@ -93,12 +93,16 @@ inline Layout make_layout(const aa_dims& d) {
   L.heads_w4 = take((size_t)3 * L.NHp * L.C / 2);  // heads as 3 bf16 planes, 16x16x32 fragments [NHp/16][C/32][3][64][8]
   L.wvg4 = take((size_t)3 * L.N5 * L.E / 2);       // W_vg (x_g GEMM) likewise [N5/16][E/32][3][64][8]
   L.wv4 = take((size_t)3 * PP * L.H / 2);          // W_v (VWv GEMM) likewise [PP/16][H/32][3][64][8]
+  L.enc_w4h = take((size_t)2 * L.H * L.C / 2);     // W_a 2^e as 2 fp16 planes (hi, lo), 16x16x32 fragments [H/16][C/32][2][64][8]
+  L.enc_w4h_sc = take(2);                          // its un-scale 2^-(e + ENC_F16_A_EXP) and the exponent e (as a float)
   L.total_floats = o;
   return L;
 }
 
 struct MP {  // resolved device pointers of the packed weights
   const bf16x8 *enc_w3, *whh3, *mlp_w3, *enc_w4, *heads_w4, *wvg4, *wv4;
+  const f16x8* enc_w4h;
+  const float* enc_w4h_sc;
   const float *enc_a_w, *enc_a_b, *heads_w, *heads_b, *wv, *wg, *ws, *wh, *whh, *wemb, *wvg, *bias5, *table, *mlp_w,
       *mlp_b, *mlp_wn, *wgs;
   const float4* mlp_gs;
@@ -116,6 +120,8 @@ inline MP resolve(const aa_model* m, const Layout& L) {
   p.heads_w4 = reinterpret_cast<const bf16x8*>(b + L.heads_w4);
   p.wvg4 = reinterpret_cast<const bf16x8*>(b + L.wvg4);
   p.wv4 = reinterpret_cast<const bf16x8*>(b + L.wv4);
+  p.enc_w4h = reinterpret_cast<const f16x8*>(b + L.enc_w4h);
+  p.enc_w4h_sc = b + L.enc_w4h_sc;
   p.heads_w = b + L.heads_w; p.heads_b = b + L.heads_b;
   p.wv = b + L.wv; p.wg = b + L.wg; p.ws = b + L.ws; p.wh = b + L.wh;
   p.whh = b + L.whh; p.wemb = b + L.wemb; p.wvg = b + L.wvg; p.bias5 = b + L.bias5; p.table = b + L.table;
@@ -180,6 +186,23 @@ __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l)
   m = (__bf16)r1;
   const float r2 = r1 - (float)m;
   l = (__bf16)r2;
+}
+
+// The encoder V GEMM's two-way fp16 split (k_enc_v4's fast path; the error argument is at the kernel).
+// Features are scaled by 2^ENC_F16_A_EXP before the split; a feature that is not below ENC_F16_A_MAX
+// in magnitude (or not finite) sends its workgroup through the bf16x3 body.  W_a is scaled at pack
+// time by the power of two 2^e that puts max|W_a| 2^e in [2^ENC_F16_W_TOP, 2^(ENC_F16_W_TOP + 1)), e
+// clamped to +-ENC_F16_W_ECLAMP (e = 0 for an all-zero or non-finite tensor).
+// (tests/test_split_f16_emulation.py reads these four lines.)
+constexpr int ENC_F16_A_EXP = 6;
+constexpr float ENC_F16_A_MAX = 512.0f;
+constexpr int ENC_F16_W_TOP = 13;
+constexpr int ENC_F16_W_ECLAMP = 64;
+// exact 2-way fp16 split of an already scaled x = h + l + r: the difference is exact in fp32 and, while
+// l is a normal fp16 number, |r| <= 2^-22 |x| (2^-25 absolute once l is subnormal)
+__device__ __forceinline__ void split2h(float x, _Float16& h, _Float16& l) {
+  h = (_Float16)x;
+  l = (_Float16)(x - (float)h);
 }
 
 // one k16 chunk of a bf16x3 GEMM: the six products with i + j <= 2, smallest first (see k_enc_v3)

@@ -162,7 +162,7 @@ AA_API int aa_pack_weights(const aa_model* m, const aa_ref_weights* w, aa_stream
  * Replaces AttentiveCNN.forward after resnet_conv (baseline_attention.py:46-62).
  * feats: [B, C, 7, 7] NCHW post-trunk features.  Outputs: a_g [B,C], V [B,P,H], v_g [B,E],
  * h0 [B,H], c0 [B,H], VWv [B,P,64] (columns >= P are zero; may be NULL).  flags: 0 or
- * AA_DECODE_FP32_ENCODER. */
+ * AA_DECODE_FP32_ENCODER or AA_DECODE_ENC_BF16X3. */
 AA_API int aa_encoder_tail(const aa_model* m, const float* feats, int32_t B, float* a_g, float* V,
                            float* v_g, float* h0, float* c0, float* VWv, int32_t flags,
                            aa_stream_t stream);
@@ -199,7 +199,8 @@ AA_API size_t aa_decode_workspace_bytes(const aa_dims* dims, int32_t B, int32_t 
 #define AA_DECODE_EXACT_VOCAB 1 /* compute every fp32 logit (fp32 MFMA GEMM + fused argmax) instead of
                                    the bf16 screen + exact fp32 rescoring; both give the same ids */
 #define AA_DECODE_FP32_ENCODER 2 /* V = relu(A W_a^T + b) on fp32 MFMA (v_mfma_f32_32x32x2f32) instead of
-                                    the default fp32-accurate 3-way-split bf16 MFMA (k_enc_v4) */
+                                    the default fp32-accurate split-operand MFMA (k_enc_v4: 2-way fp16
+                                    split, 3-way bf16 split for out-of-range features and in k_enc_v3) */
 #define AA_DECODE_ONE_STREAM 512 /* decode plans: capture the whole decode on one stream (no side-stream
                                      branch for the encoder's a_g work); for several plans in flight */
 #define AA_DECODE_SPLIT_RESCORE 1024 /* rescore each step in its own launch (k_vrescore) instead of inside
@@ -217,6 +218,10 @@ AA_API size_t aa_decode_workspace_bytes(const aa_dims* dims, int32_t B, int32_t 
                                    flag above.  The flag MUST match how the model was packed: a
                                    baseline-packed model decoded without it (or an adaptive one with it)
                                    computes garbage silently. */
+#define AA_DECODE_ENC_BF16X3 16384 /* test hook: every k_enc_v4 workgroup computes V with the 3-way bf16
+                                      split (six products) instead of the default 2-way fp16 split (three),
+                                      i.e. the body a workgroup whose features leave the fp16 path's range
+                                      falls back to; a_g is bit-identical, V agrees to fp32-GEMM accuracy */
 
 /* Whole greedy decode = Encoder2Decoder.sampler(images, max_len=T) (adaptive_attention.py:168-216,
  * with the baseline's states transpose, baseline_attention.py:251-252).  feats [B,C,7,7];

@@ -53,7 +53,10 @@ extern "C" int kb_time(const aa_model* m, const float* feats, void* ws, int B, i
       hipLaunchKernelGGL(k_enc_v3, dim3(((M + EV_BM - 1) / EV_BM) * (H / EV_BN)), dim3(256), 0, s, feats, B, L.C, H, p.enc_w3, p.enc_a_b, w.e.V);
     } else if (!strcmp(which, "enc_v4")) {
       hipLaunchKernelGGL((k_enc_v4<32 / ENC4_NW, ENC4_NW>), dim3((B * P + E4_ROWS - 1) / E4_ROWS), dim3(64 * ENC4_NW), 0,
-                         s, feats, B, L.C, p.enc_w4, p.enc_a_b, w.e.V, w.e.a_g);
+                         s, feats, B, L.C, p.enc_w4, p.enc_w4h, p.enc_w4h_sc, p.enc_a_b, w.e.V, w.e.a_g, 0);
+    } else if (!strcmp(which, "enc_v4_x3")) {  // the bf16x3 body in every workgroup
+      hipLaunchKernelGGL((k_enc_v4<32 / ENC4_NW, ENC4_NW>), dim3((B * P + E4_ROWS - 1) / E4_ROWS), dim3(64 * ENC4_NW), 0,
+                         s, feats, B, L.C, p.enc_w4, p.enc_w4h, p.enc_w4h_sc, p.enc_a_b, w.e.V, w.e.a_g, 1);
     } else {
       return false;
     }
