@@ -106,6 +106,12 @@ class SampleOpts(Structure):
                 ("theta", c_void_p)]
 
 
+class BeamOpts(Structure):
+    """aa_beam_opts: groups (divides K), diversity, length_penalty, optional lengths / rank_scores / group outputs."""
+    _fields_ = [("groups", c_int32), ("diversity", c_float), ("length_penalty", c_float), ("lengths", c_void_p),
+                ("rank_scores", c_void_p), ("group", c_void_p)]
+
+
 CIDER_MAX_T = 64
 
 
@@ -168,6 +174,9 @@ SIGNATURES = {
     "aa_beam_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32, c_int32]),
     "aa_beam_decode": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p]),
+    "aa_beam_decode_ex": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p,
+                                  POINTER(BeamOpts)]),
     "aa_sample_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "aa_sample_decode": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_float, c_uint64, c_int64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p]),

@@ -514,7 +514,8 @@ class Encoder2Decoder(nn.Module):
 
     @torch.no_grad()
     def beam_search(self, images: torch.Tensor, max_len: int = 20, beam_size: int = 3, end_id: int = 2,
-                    exact_vocab: Optional[bool] = None, fast: bool = False, vocab_events=None):
+                    exact_vocab: Optional[bool] = None, fast: bool = False, vocab_events=None, *, groups: int = 1,
+                    diversity: float = 0.0, length_penalty: float = 0.0, return_details: bool = False):
         """Beam-search decode (BASELINE config 4; not in the reference, semantics in
         include/adaptive_amd.h and DESIGN.md) -> (ids [B,T], alpha [B,T,49], beta [B,T,1],
         seqs [B,K,T], scores [B,K]): ids / alpha / beta of the best final beam, then every final
@@ -527,7 +528,37 @@ class Encoder2Decoder(nn.Module):
         log-sum-exp summaries -- fp32-accurate but not bitwise, so a near-tie between two candidates
         can be decided differently (opt-in speed mode).  ``vocab_events``: address of 2 * max_len raw
         hipEvent handles (adaptive_amd.hip_events.EventArray.ptr) recorded around each step's vocab
-        stage, for per-launch timing."""
+        stage, for per-launch timing.
+
+        Diverse groups and length normalisation (keyword-only): ``groups=G`` (a
+        divisor of ``beam_size``) splits the K beams into G groups of K/G slots, a beam's parent always
+        in its own group; within a step the groups select in order, group g ranking its candidates by
+        ``score - diversity * n[v]``, n[v] the number of earlier groups' survivors of this step that newly
+        emitted token v (Hamming diversity; a finished beam's carried ``<end>`` is neither penalised nor
+        counted).  The penalty steers the selection only: ``scores`` stay raw cumulative
+        log-probabilities.  ``length_penalty=a`` ranks the final beams by ``score / len**a``, ``len`` the
+        position of the first ``end_id`` + 1 (``max_len`` without one); ids / alpha / beta follow the
+        first.  ``return_details=True`` appends ``lengths [B,K]`` int32, ``rank_scores [B,K]`` fp32 and
+        ``group [B,K]`` int32, in the order of ``seqs``.  With all four at their defaults the call is the
+        plain one, bit for bit; with ``diversity=0`` the beams of a group are those of
+        ``beam_search(beam_size=K/G)``."""
+        import math
+        K = int(beam_size)
+        if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or int(groups) < 1:
+            raise ValueError(f"groups must be an integer >= 1, got {groups!r}")
+        G = int(groups)
+        if K % G != 0:
+            raise ValueError(f"groups must divide beam_size, got groups={G}, beam_size={K}")
+        f32 = {}
+        for name, val in (("diversity", diversity), ("length_penalty", length_penalty)):
+            try:
+                with np.errstate(over="ignore", under="ignore"):
+                    f32[name] = float(np.float32(val))  # the value the kernel computes with
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be a finite number >= 0, got {val!r}") from None
+            if isinstance(val, bool) or not (math.isfinite(f32[name]) and f32[name] >= 0.0):  # NaN fails
+                raise ValueError(f"{name} must be finite and >= 0 (as fp32), got {val!r}")
+        plain = G == 1 and f32["diversity"] == 0.0 and f32["length_penalty"] == 0.0 and not return_details
         check = False
         if exact_vocab is not None:
             if exact_vocab and fast:
@@ -536,7 +567,7 @@ class Encoder2Decoder(nn.Module):
         images = self._check_images(self.features(images))
         model = self._model_struct()
         lib = _lib.load()
-        B, T, K, dev = images.size(0), int(max_len), int(beam_size), images.device
+        B, T, dev = images.size(0), int(max_len), images.device
         if not 1 <= K <= _lib.MAX_BEAM:
             raise ValueError(f"beam_size must be in [1, {_lib.MAX_BEAM}], got {K}")
         ids = torch.empty(B, T, dtype=torch.int64, device=dev)
@@ -548,15 +579,26 @@ class Encoder2Decoder(nn.Module):
         if nbytes == 0 and B > 0 and T > 0:
             raise ValueError(f"unsupported beam configuration B={B} T={T} K={K} for {self.dims}")
         ws = self._workspace(nbytes, dev)
+        details = ()
+        if return_details:
+            details = (torch.empty(B, K, dtype=torch.int32, device=dev), torch.empty(B, K, dtype=torch.float32, device=dev),
+                       torch.empty(B, K, dtype=torch.int32, device=dev))
         with torch.cuda.device(dev):
-            rc = lib.aa_beam_decode(model, images.data_ptr(), B, T, K, int(end_id), ids.data_ptr(), seqs.data_ptr(),
-                                    scores.data_ptr(), alpha.data_ptr(), beta.data_ptr(), _lib.ptr(ws),
-                                    ws.numel() if ws is not None else 0,
-                                    (_lib.BEAM_FAST if fast else 0) | (_lib.DECODE_EXACT_VOCAB if check else 0),
-                                    _lib.stream_handle(),
-                                    vocab_events)
+            args = (model, images.data_ptr(), B, T, K, int(end_id), ids.data_ptr(), seqs.data_ptr(),
+                    scores.data_ptr(), alpha.data_ptr(), beta.data_ptr(), _lib.ptr(ws),
+                    ws.numel() if ws is not None else 0,
+                    (_lib.BEAM_FAST if fast else 0) | (_lib.DECODE_EXACT_VOCAB if check else 0),
+                    _lib.stream_handle(),
+                    vocab_events)
+            if plain:
+                rc = lib.aa_beam_decode(*args)
+            else:
+                lens, ranks, grp = details or (None, None, None)
+                opts = _lib.BeamOpts(G, f32["diversity"], f32["length_penalty"], _lib.ptr(lens), _lib.ptr(ranks),
+                                     _lib.ptr(grp))
+                rc = lib.aa_beam_decode_ex(*args, ctypes.byref(opts))
         _lib.check(rc, "beam_decode")
-        return ids, alpha, beta, seqs, scores
+        return (ids, alpha, beta, seqs, scores) + details
 
     @torch.no_grad()
     def sample(self, images: torch.Tensor, max_len: int = 20, temperature: float = 1.0, seed: int = 0,

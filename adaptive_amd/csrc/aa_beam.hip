@@ -20,6 +20,10 @@
 // through the launch functions of aa_internal.hpp.  The two exact fp32 vocab GEMMs are this unit's:
 // k_vexact (sampling's too) and k_vocab, whose arithmetic it shares (the greedy path's exact-vocab
 // stage and aa_vocab_logits call vocab_launch).
+//
+// aa_beam_decode_ex (diverse groups, length-normalised final ranking; semantics in adaptive_amd.h,
+// restated by tests/beam_div_oracle.py) runs the same step with k_beam_select3<true> and
+// k_beam_final_ex; aa_beam_decode keeps k_beam_select3<false> and k_beam_final.
 #include "aa_internal.hpp"
 
 namespace aa {
@@ -79,6 +83,71 @@ __global__ __launch_bounds__(256) void k_beam_final(int K, int T, int R, const i
       const int col = htok[(int64_t)t * R + r];
       const int pk = hpar[(int64_t)t * R + r];
       if (seqs) seqs[((int64_t)b * K + tid) * T + t] = col;
+      if (tid == 0) {
+        if (ids) ids[(int64_t)b * T + t] = col;
+        path[(int64_t)b * T + t] = b * K + pk;
+      }
+      j = pk;
+    }
+  }
+  if (!alpha && !beta) return;
+  __syncthreads();
+  for (int i = tid; i < T * P; i += 256) {
+    const int t = i / P, q = i % P;
+    const int r = path[(int64_t)b * T + t];
+    if (alpha) alpha[((int64_t)b * T + t) * P + q] = ahist[((int64_t)t * R + r) * P + q];
+    if (beta && q == 0) beta[(int64_t)b * T + t] = bhist[(int64_t)t * R + r];
+  }
+}
+
+// k_beam_final with a length-normalised ranking (aa_beam_decode_ex).  Thread j < K traces slot j back
+// for len = the position of its first end_id + 1 (T if there is none; end_id < 0 matches no token),
+// rank = cum / len^lp in fp32 (lp == 0: powf gives 1, rank is cum itself); the K slots are ordered by
+// rank descending, ties to the lower slot, and thread i < K then traces the slot that ranks i-th into
+// row i of the outputs (group = slot / Kg).  ids, alpha and beta follow row 0.
+__global__ __launch_bounds__(256) void k_beam_final_ex(int K, int Kg, int T, int R, int end_id, float lp,
+                                                       const int* __restrict__ htok, const int* __restrict__ hpar,
+                                                       const float* __restrict__ cum, const float* __restrict__ ahist,
+                                                       const float* __restrict__ bhist, int* __restrict__ path,
+                                                       int64_t* __restrict__ ids, int64_t* __restrict__ seqs,
+                                                       float* __restrict__ scores, float* __restrict__ alpha,
+                                                       float* __restrict__ beta, int* __restrict__ lengths,
+                                                       float* __restrict__ rank_scores, int* __restrict__ group) {
+  __shared__ float s_rank[BEAM_MAX];
+  __shared__ int s_len[BEAM_MAX], s_slot[BEAM_MAX];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid < K) {
+    int j = tid, first = T - 1;
+    for (int t = T - 1; t >= 0; --t) {
+      const int r = b * K + j;
+      if (htok[(int64_t)t * R + r] == end_id) first = t;
+      j = hpar[(int64_t)t * R + r];
+    }
+    s_len[tid] = first + 1;
+    s_slot[tid] = tid;  // a valid slot whatever the ranks are (NaN ranks would leave positions unfilled)
+    s_rank[tid] = cum[b * K + tid] / powf((float)(first + 1), lp);
+  }
+  __syncthreads();
+  if (tid < K) {
+    const float mine = s_rank[tid];
+    int pos = 0;
+    for (int j = 0; j < K; ++j) pos += (s_rank[j] > mine || (s_rank[j] == mine && j < tid)) ? 1 : 0;
+    s_slot[pos] = tid;
+  }
+  __syncthreads();
+  if (tid < K) {
+    const int slot = s_slot[tid];
+    const int64_t o = (int64_t)b * K + tid;
+    if (scores) scores[o] = cum[b * K + slot];
+    if (lengths) lengths[o] = s_len[slot];
+    if (rank_scores) rank_scores[o] = s_rank[slot];
+    if (group) group[o] = slot / Kg;
+    int j = slot;
+    for (int t = T - 1; t >= 0; --t) {
+      const int r = b * K + j;
+      const int col = htok[(int64_t)t * R + r];
+      const int pk = hpar[(int64_t)t * R + r];
+      if (seqs) seqs[o * T + t] = col;
       if (tid == 0) {
         if (ids) ids[(int64_t)b * T + t] = col;
         path[(int64_t)b * T + t] = b * K + pk;
@@ -494,12 +563,21 @@ __global__ __launch_bounds__(1024) void k_vbeam5(int R, int V, int Vp, const bf1
 // ls = log(sum_g s_g exp(m_g - M)) (lane-strided granules in order, then the wave tree); the row's
 // top-K tokens lie in the granules whose max reaches the K-th largest granule max (ties kept), so
 // only those granules' logits are read.  Wave 0 lane 0 then merges the image's K x K candidates.
+//
+// GROUPED (diverse beam search, aa_beam_decode_ex): the K slots are G = K / Kg groups of Kg, a beam's
+// parent is in its own group, and at step 0 the first slot of every group is live.  The per-row phase
+// is the plain one: group g ranks by raw - lam n[v], n[v] the number of earlier groups' survivors of
+// this step that newly emitted v, so at most K - Kg tokens carry a penalty; a candidate outside its
+// row's raw top K has K raw-better candidates in its row, at least Kg of them unpenalised, which beat
+// it on the augmented key as well (ties included: the tie order is the same q V + v).  Only the merge
+// differs: see below.  Kg and lam are read by the GROUPED instantiation alone.
+template <bool GROUPED>
 __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int R, int t, int end_id,
                                                       const float* __restrict__ logits,
                                                       const float2* __restrict__ gsum, float* __restrict__ cum,
                                                       int* __restrict__ fin, int64_t* __restrict__ tok,
                                                       int* __restrict__ par, int* __restrict__ htok,
-                                                      int* __restrict__ hpar) {
+                                                      int* __restrict__ hpar, int Kg, float lam) {
   constexpr int GPL = 8;  // granule summaries held per lane: NG <= 512 (V <= 16384)
   __shared__ float s_mx[BEAM_MAX], s_ls[BEAM_MAX];
   __shared__ uint64_t s_top[BEAM_MAX][BEAM_MAX];
@@ -507,7 +585,7 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
   const int b = blockIdx.x, lane = threadIdx.x & 63, k = threadIdx.x >> 6;
   const int NG = Vp / 32;
   const int row = b * K + k;
-  const bool live = !(t == 0 && k > 0) && fin[row] == 0;  // uniform over the wave
+  const bool live = !(t == 0 && (GROUPED ? k % Kg != 0 : k > 0)) && fin[row] == 0;  // uniform over the wave
   if (live) {
     const float2* gs = gsum + (int64_t)row * NG;
     float gm[GPL], gv[GPL];
@@ -583,7 +661,7 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
     const int q = lane / K, j = lane - q * K;
     uint64_t key = 0;
     int qfin = 0;
-    if (q < K && !(t == 0 && q > 0)) {
+    if (q < K && !(t == 0 && (GROUPED ? q % Kg != 0 : q > 0))) {
       const float ocum = cum[b * K + q];
       qfin = fin[b * K + q];
       if (qfin) {
@@ -596,19 +674,55 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
         if (tk != 0) key = argmax_key((ocum + ((xv - s_mx[q]) - s_ls[q])) + 0.0f, q * V + (int)key_token(tk));
       }
     }
-    for (int jj = 0; jj < K; ++jj) {
-      const uint64_t best = wave_max_u64(key);
-      if (key == best && best != 0) {  // candidates are distinct (distinct q V + v)
-        const int cf = (int)(0xFFFFFFFFu - (uint32_t)best);
-        const int pk = cf / V, c = cf - pk * V, r = b * K + jj;
-        cum[r] = key_value((uint32_t)(best >> 32));
-        fin[r] = (qfin || c == end_id) ? 1 : 0;
-        tok[r] = c;
-        par[r] = b * K + pk;
-        htok[(int64_t)t * R + r] = c;
-        hpar[(int64_t)t * R + r] = pk;
-        key = 0;
+    if constexpr (!GROUPED) {
+      for (int jj = 0; jj < K; ++jj) {
+        const uint64_t best = wave_max_u64(key);
+        if (key == best && best != 0) {  // candidates are distinct (distinct q V + v)
+          const int cf = (int)(0xFFFFFFFFu - (uint32_t)best);
+          const int pk = cf / V, c = cf - pk * V, r = b * K + jj;
+          cum[r] = key_value((uint32_t)(best >> 32));
+          fin[r] = (qfin || c == end_id) ? 1 : 0;
+          tok[r] = c;
+          par[r] = b * K + pk;
+          htok[(int64_t)t * R + r] = c;
+          hpar[(int64_t)t * R + r] = pk;
+          key = 0;
+        }
       }
+    } else {
+      // The groups in turn, Kg rounds each (K rounds in all, as above) over the lanes of the group's own
+      // rows.  A lane keeps its raw key and counts in cnt the earlier groups' survivors that newly
+      // emitted its token; a round compares raw - lam cnt under the same tie order, and the winner
+      // writes its raw score.  A carried-over <end> (qfin) holds no token: never penalised, never
+      // counted.  After a pick the winner's token is broadcast to the lanes of the later groups.
+      const int ctok = (key != 0 && !qfin) ? (int)(0xFFFFFFFFu - (uint32_t)key) - q * V : -1;
+      const int lg = q / Kg;
+      int cnt = 0;
+      for (int g = 0; g < K / Kg; ++g)
+        for (int jj = 0; jj < Kg; ++jj) {
+          uint64_t akey = 0;
+          if (key != 0 && lg == g)
+            akey = argmax_key((key_value((uint32_t)(key >> 32)) - lam * (float)cnt) + 0.0f,
+                              (int)(0xFFFFFFFFu - (uint32_t)key));
+          const uint64_t best = wave_max_u64(akey);
+          const bool won = akey == best && best != 0;  // one lane at most: distinct q V + v
+          const uint64_t wm = __ballot(won);
+          if (won) {
+            const int cf = (int)(0xFFFFFFFFu - (uint32_t)key);
+            const int pk = cf / V, c = cf - pk * V, r = b * K + g * Kg + jj;
+            cum[r] = key_value((uint32_t)(key >> 32));
+            fin[r] = (qfin || c == end_id) ? 1 : 0;
+            tok[r] = c;
+            par[r] = b * K + pk;
+            htok[(int64_t)t * R + r] = c;
+            hpar[(int64_t)t * R + r] = pk;
+            key = 0;
+          }
+          if (wm != 0) {
+            const int wtok = __shfl(ctok, __ffsll((unsigned long long)wm) - 1, 64);
+            if (wtok >= 0 && ctok == wtok && lg > g) ++cnt;
+          }
+        }
     }
   }
 }
@@ -682,15 +796,24 @@ size_t aa_beam_workspace_bytes(const aa_dims* d, int32_t B, int32_t T, int32_t K
   return n;
 }
 
-int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
-                   int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
-                   size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events) {
+// aa_beam_decode (opts == nullptr: the plain selection and final kernels) and aa_beam_decode_ex
+static int beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
+                       int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
+                       size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events,
+                       const aa_beam_opts* opts) {
   Layout L;
   int rc = check_model(m, &L);
   if (rc) return rc;
   rc = beam_check(&m->dims, B, T, K);
   if (rc) return rc;
   if (end_id >= L.V) return AA_ERR_SHAPE;
+  if (opts) {
+    if (opts->groups < 1 || K % opts->groups != 0) return AA_ERR_SHAPE;
+    // finite and >= 0 (a NaN fails both comparisons)
+    if (!(opts->diversity >= 0.f) || !(opts->diversity <= 3.402823466e38f)) return AA_ERR_SHAPE;
+    if (!(opts->length_penalty >= 0.f) || !(opts->length_penalty <= 3.402823466e38f)) return AA_ERR_SHAPE;
+  }
+  const int Kg = opts ? K / opts->groups : K;
   if (B == 0 || T == 0) return AA_OK;
   if (!feats || !workspace) return AA_ERR_NULL;
   if (!al16(feats) || !al16(workspace)) return AA_ERR_ALIGN;
@@ -717,6 +840,16 @@ int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, 
   fill_tok_launch(w.tok0, R, 1, s);  // <start>
   AA_TRY(hipMemsetAsync(w.cum, 0, sizeof(float) * R, s));
   AA_TRY(hipMemsetAsync(w.fin, 0, sizeof(int) * R, s));
+  auto select = [&](int t) {
+    if (opts)
+      hipLaunchKernelGGL(k_beam_select3<true>, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t,
+                         end_id < 0 ? -1 : end_id, w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar, Kg,
+                         opts->diversity);
+    else
+      hipLaunchKernelGGL(k_beam_select3<false>, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t,
+                         end_id < 0 ? -1 : end_id, w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar, 0,
+                         0.f);
+  };
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     lstm_atten_launch(L, p,
@@ -737,8 +870,7 @@ int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, 
         vexact_launch(L, p, R, r.u, w.logits, w.gsum, s, vocab_events, 2 * t);
       }
       if (flags & AA_DECODE_EXACT_VOCAB) rec(vocab_events, 2 * t + 1, s);
-      hipLaunchKernelGGL(k_beam_select3, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t, end_id < 0 ? -1 : end_id,
-                         w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar);
+      select(t);
     } else {
       // 256 x 256 tiles when the padded vocabulary is whole 256-column tiles (V = 10,123: 40 of them)
       const bool wide = L.Vp % 256 == 0;  // else 128 x 128 tiles (k_vbeam4)
@@ -750,11 +882,30 @@ int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, 
           AA_TLAUNCH(vocab_events, 2 * t, k_vbeam4<h.value>, dim3(((R + 127) / 128) * (L.Vp / 128)), dim3(256), 0, s,
                      R, L.V, L.Vp, (const bf16x8*)w.u3, p.mlp_w3, p.mlp_b, w.logits, w.gsum);
       });
-      hipLaunchKernelGGL(k_beam_select3, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t, end_id < 0 ? -1 : end_id,
-                         w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar);
+      select(t);
     }
   }
-  hipLaunchKernelGGL(k_beam_final, dim3(B), dim3(256), 0, s, K, T, R, w.htok, w.hpar, w.cum, w.ahist, w.bhist, w.path,
-                     ids, seqs, scores, alpha, beta);
+  if (opts)
+    hipLaunchKernelGGL(k_beam_final_ex, dim3(B), dim3(256), 0, s, K, Kg, T, R, end_id < 0 ? -1 : end_id,
+                       opts->length_penalty, w.htok, w.hpar, w.cum, w.ahist, w.bhist, w.path, ids, seqs, scores, alpha,
+                       beta, opts->lengths, opts->rank_scores, opts->group);
+  else
+    hipLaunchKernelGGL(k_beam_final, dim3(B), dim3(256), 0, s, K, T, R, w.htok, w.hpar, w.cum, w.ahist, w.bhist,
+                       w.path, ids, seqs, scores, alpha, beta);
   return launch_status();
+}
+
+int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
+                   int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
+                   size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events) {
+  return beam_decode(m, feats, B, T, K, end_id, ids, seqs, scores, alpha, beta, workspace, workspace_bytes, flags,
+                     stream, vocab_events, nullptr);
+}
+
+int aa_beam_decode_ex(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
+                      int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
+                      size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events,
+                      const aa_beam_opts* opts) {
+  return beam_decode(m, feats, B, T, K, end_id, ids, seqs, scores, alpha, beta, workspace, workspace_bytes, flags,
+                     stream, vocab_events, opts);
 }

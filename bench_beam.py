@@ -8,6 +8,11 @@ all K beams decoded), ms per batch, and the CPU restatement (oracle BeamOracle) 
 sample on this host.
 
     python bench_beam.py [--steps 10] [--warmup 2] [--batch 512] [--beam 3] [--T 20] [--no-cpu-baseline]
+
+--groups G / --diversity L / --length-penalty A (any of them given): the line is that of the grouped
+decode (aa_beam_decode_ex: k_beam_select3<true>, k_beam_final_ex), and its "ab" entry compares it with the
+plain call (aa_beam_decode) at the same beam width in this process: --regions alternating regions of
+--steps calls each, the median region of either, and their ratio.
 """
 from __future__ import annotations
 
@@ -63,25 +68,54 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fast", action="store_true", help="opt-in bf16x3 logits (AA_BEAM_FAST) instead of the exact "
                     "fp32 default")
+    ap.add_argument("--groups", type=int, default=None, help="diverse beam search: G groups of beam / G slots")
+    ap.add_argument("--diversity", type=float, default=None, help="Hamming diversity penalty per earlier group's pick")
+    ap.add_argument("--length-penalty", type=float, default=None, help="rank the final beams by score / len^A")
+    ap.add_argument("--regions", type=int, default=5, help="grouped decode: alternating regions per side of the A/B")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, K, T = args.batch, args.beam, args.T
+    grouped = not (args.groups is None and args.diversity is None and args.length_penalty is None)
+    # the grouped decode goes through aa_beam_decode_ex whatever the values (return_details forces it)
+    div = ({"groups": args.groups or 1, "diversity": args.diversity or 0.0, "length_penalty": args.length_penalty or 0.0,
+            "return_details": True} if grouped else {})
     model = Encoder2Decoder(Config()).to(dev).load_synthetic(123)
     feats = synthetic_features(B, dev, seed=0)
+
+    def region(kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            o = model.beam_search(feats, T, K, fast=args.fast, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, o
+
     for _ in range(args.warmup):
-        model.beam_search(feats, T, K, fast=args.fast)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out = model.beam_search(feats, T, K, fast=args.fast)
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
+        model.beam_search(feats, T, K, fast=args.fast, **div)
+    el, out = region(div)
+    ab = None
+    if grouped:
+        for _ in range(args.warmup):
+            model.beam_search(feats, T, K, fast=args.fast)
+        plain_s, div_s = [], []
+        for _ in range(max(1, args.regions)):
+            plain_s.append(region({})[0])
+            div_s.append(region(div)[0])
+        mp, md = float(np.median(plain_s)), float(np.median(div_s))
+        ab = {"regions": len(div_s), "calls_per_region": args.steps,
+              "plain": {"path": "aa_beam_decode (k_beam_select3<false>, k_beam_final)", "ms_per_call": 1e3 * mp / args.steps,
+                        "captions_per_s": B * args.steps / mp, "region_ms": [1e3 * x for x in plain_s]},
+              "grouped": {"path": "aa_beam_decode_ex (k_beam_select3<true>, k_beam_final_ex)",
+                          "ms_per_call": 1e3 * md / args.steps, "captions_per_s": B * args.steps / md,
+                          "region_ms": [1e3 * x for x in div_s]},
+              "grouped_over_plain_time": md / mp}
+        el = md
     # traced pass (the same calls again): HIP events on the launch stream around every step's vocab
     # stage -- the dominant kernel (k_vexact: exact fp32 logits + granule summaries; fast mode:
     # k_vbeam5 / k_vbeam4) -- for its average launch duration
     evs = [EventArray(2 * T) for _ in range(args.steps)]
     for ev in evs:
-        model.beam_search(feats, T, K, fast=args.fast, vocab_events=ev.ptr)
+        model.beam_search(feats, T, K, fast=args.fast, vocab_events=ev.ptr, **div)
     torch.cuda.synchronize()
     durs = [d for ev in evs for d in ev.pair_durations_ms()]
     avg_ms = float(np.mean(durs))
@@ -109,8 +143,11 @@ def main():
                       "beam": K, "T": T, "rows": B * K,
                       "vocab_kernel": "bf16x3 k_vbeam5 (256x256)"
                       if args.fast else "exact fp32: k_vexact (fused fp32 MFMA logits + granule summaries)",
-                      "mode": "fast (opt-in bf16x3)" if args.fast else "exact (default)"},
+                      "mode": "fast (opt-in bf16x3)" if args.fast else "exact (default)",
+                      **({k: div[k] for k in ("groups", "diversity", "length_penalty")} if grouped else {})},
            "best_score_mean": float(out[4][:, 0].mean().item()), "roofline": roofline, "cpu_baseline": None}
+    if ab:
+        res["ab"] = ab
     if not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(K, T, args.cpu_sample, args.cpu_budget)
         res["speedup_vs_cpu"] = res["value"] / res["cpu_baseline"]["value"]

@@ -357,6 +357,43 @@ AA_API int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int3
                           float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
                           aa_stream_t stream, aa_event_t* vocab_events);
 
+/* ---- diverse beam groups and a length-normalised final ranking ----------------------------------
+ * Additions to the beam decode; aa_beam_decode keeps its signature and behaviour (it is
+ * aa_beam_decode_ex with opts == NULL).  Semantics defined here and in tests/beam_div_oracle.py.
+ * groups = G divides K (Kg = K / G): group g owns the slots g Kg .. (g + 1) Kg - 1 of an image, and a
+ * beam's parent is always in its own group.  Per step the raw candidates are aa_beam_decode's (the
+ * same fp32 expression on the same logits; a finished beam's single carry-over end_id at its unchanged
+ * score), except that at step 0 slot 0 of every group is live.  The groups select in order g = 0 ..
+ * G - 1 over a per-image token count n[v] that starts at 0 every step (Hamming diversity, Vijayakumar
+ * et al.): group g ranks its Kg V candidates by raw - diversity * n[v] in fp32 (a carry-over is never
+ * penalised), descending, ties to the smaller q V + v with q the parent's slot in the image; the best
+ * Kg survive into the group's slots in that order, each with its raw score as the new cumulative
+ * score (the penalty steers the selection only); then n[v] += 1 for every survivor that newly emitted
+ * v (carry-overs do not count).
+ * Final ranking: len = the position of the beam's first end_id + 1, or T without one (always T when
+ * end_id < 0); rank = cum / len^length_penalty in fp32; the K beams of an image come out by rank
+ * descending, ties to the lower slot.  seqs and scores (the raw cum) are in that order, ids / alpha /
+ * beta follow the first, and lengths / rank_scores / group ([B,K], each may be NULL) give every
+ * beam's len, rank and group in the same order.
+ * groups = 1, diversity = 0, length_penalty = 0 is aa_beam_decode's result, by other kernels.  With
+ * diversity = 0 the beams of group g, in rank order, are those of a K / G-beam decode.
+ * The vocabulary stages (default, AA_DECODE_EXACT_VOCAB, AA_BEAM_FAST) and the workspace
+ * (aa_beam_workspace_bytes) are aa_beam_decode's.  Checks: as aa_beam_decode, and before the B == 0 /
+ * T == 0 return AA_ERR_SHAPE for groups < 1, K % groups != 0, or a diversity or length_penalty that
+ * is negative or not finite. */
+typedef struct aa_beam_opts {
+  int32_t groups;       /* >= 1, divides K */
+  float diversity;      /* >= 0; 0: off */
+  float length_penalty; /* >= 0; 0: rank by the raw score */
+  int32_t* lengths;     /* [B, K] or NULL */
+  float* rank_scores;   /* [B, K] or NULL */
+  int32_t* group;       /* [B, K] or NULL */
+} aa_beam_opts;
+AA_API int aa_beam_decode_ex(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K,
+                             int32_t end_id, int64_t* ids, int64_t* seqs, float* scores, float* alpha,
+                             float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
+                             aa_stream_t stream, aa_event_t* vocab_events, const aa_beam_opts* opts);
+
 /* ---- seeded temperature-sampling decode ---------------------------------------------------------
  * Not in the reference: semantics defined here and in tests/sample_oracle.py SampleOracle.  One
  * caption per image drawn from the model's own distribution by Gumbel-max over the exact fp32 logits
