@@ -296,6 +296,7 @@ struct BoolC {
 // stage s instead of after the pair's last MFMA -- 16 + 16 VGPRs of W.  128 VGPRs and 20 B/lane of
 // scratch at 16 waves, k_enc_v4 175.7 / 178.9 -> 182.1 / 182.6 us in A/B: not kept.  The W loads'
 // latency is not what the stage waits for.)
+// (Also tried and not kept: 64-channel stages, and every thread staging four values per stage)
 
 template <int NCB, int NW = 8>
 __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ feats, int B, int C,
@@ -396,10 +397,7 @@ __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ fe
     for (int s = 0; s < ns; ++s) {
       const int buf = s & 1, s1 = s + 1 < ns ? s + 1 : ns - 1, s2 = s + 2 < ns ? s + 2 : ns - 1;
       // A of stage s+1 (in ra) into the other buffer: its last readers (stage s-1) passed the barrier
-      if (stg) {
-        lstore_a(buf ^ 1);
-        gload_a(s2);
-      }
+      if (stg) lstore_a(buf ^ 1);
       __builtin_amdgcn_sched_barrier(0);
       const __bf16* Ab = &As[buf][0][fo];
 #pragma unroll
@@ -439,6 +437,16 @@ __global__ __launch_bounds__(64 * NW) void k_enc_v4(const float* __restrict__ fe
           }
           acc[rb][c0] = x;
           acc[rb][c1] = y;
+          // Stage s+2's features are asked for here, behind the first row block's MFMAs.  Issued at the
+          // top of the stage (inside `if (stg)`, which the other waves skip) they were drained at once:
+          // where the two paths join, the waits for the W fragments in front of the first MFMAs must hold
+          // for both, vmcnt counts in order, and so `vmcnt(0)` also waited for the eight loads a staging
+          // wave had just issued.  Here nothing waits for them before the next stage's lstore_a.
+          if (cp == 0 && rb == 0) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (stg) gload_a(s2);
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
         gload_w(s1, 2 * cp);
         gload_w(s1, 2 * cp + 1);
