@@ -37,6 +37,8 @@ BEAM_FAST = 256
 TRAIN_BF16 = 128
 TRAIN_SENTINEL_H0 = 64  # the sentinel gate without its h_{t-1} term, as the one-token decode step
 MAX_BEAM = 8
+MAX_BEAM_SUPPRESS = 64  # ids per list of aa_beam_constraints
+MAX_BEAM_NGRAM_T = 256  # max_len with no_repeat_ngram > 0
 
 
 class Dims(Structure):
@@ -112,6 +114,13 @@ class BeamOpts(Structure):
                 ("rank_scores", c_void_p), ("group", c_void_p)]
 
 
+class BeamConstraints(Structure):
+    """aa_beam_constraints: suppress_ids / no_end_after (device int32 arrays with their counts), min_length,
+    no_repeat_ngram."""
+    _fields_ = [("suppress_ids", c_void_p), ("n_suppress", c_int32), ("min_length", c_int32),
+                ("no_repeat_ngram", c_int32), ("no_end_after", c_void_p), ("n_no_end_after", c_int32)]
+
+
 CIDER_MAX_T = 64
 
 
@@ -177,6 +186,13 @@ SIGNATURES = {
     "aa_beam_decode_ex": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p,
                                   POINTER(BeamOpts)]),
+    "aa_beam_decode_cx": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p,
+                                  POINTER(BeamOpts), POINTER(BeamConstraints)]),
+    "aa_beam_select_step_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "aa_beam_select_step": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, POINTER(BeamOpts), POINTER(BeamConstraints), c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "aa_sample_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "aa_sample_decode": (c_int, [POINTER(Model), c_void_p, c_int32, c_int32, c_float, c_uint64, c_int64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p]),

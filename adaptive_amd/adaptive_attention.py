@@ -515,7 +515,8 @@ class Encoder2Decoder(nn.Module):
     @torch.no_grad()
     def beam_search(self, images: torch.Tensor, max_len: int = 20, beam_size: int = 3, end_id: int = 2,
                     exact_vocab: Optional[bool] = None, fast: bool = False, vocab_events=None, *, groups: int = 1,
-                    diversity: float = 0.0, length_penalty: float = 0.0, return_details: bool = False):
+                    diversity: float = 0.0, length_penalty: float = 0.0, return_details: bool = False,
+                    suppress_ids=(), min_length: int = 0, no_repeat_ngram: int = 0, no_end_after=()):
         """Beam-search decode (BASELINE config 4; not in the reference, semantics in
         include/adaptive_amd.h and DESIGN.md) -> (ids [B,T], alpha [B,T,49], beta [B,T,1],
         seqs [B,K,T], scores [B,K]): ids / alpha / beta of the best final beam, then every final
@@ -541,7 +542,22 @@ class Encoder2Decoder(nn.Module):
         first.  ``return_details=True`` appends ``lengths [B,K]`` int32, ``rank_scores [B,K]`` fp32 and
         ``group [B,K]`` int32, in the order of ``seqs``.  With all four at their defaults the call is the
         plain one, bit for bit; with ``diversity=0`` the beams of a group are those of
-        ``beam_search(beam_size=K/G)``."""
+        ``beam_search(beam_size=K/G)``.
+
+        Constraints (keyword-only, all off by default; include/adaptive_amd.h).  A
+        live hypothesis at step t with its own tokens ``y_0 .. y_{t-1}`` (``y_{-1}`` = ``<start>`` = 1) may
+        not emit v if: v is in ``suppress_ids`` (``<unk>``, ``<start>``, ...); v is ``end_id`` and
+        ``t < min_length`` (every caption has ``min_length`` tokens before ``<end>``); v is ``end_id`` and
+        ``y_{t-1}`` is in ``no_end_after`` (no caption ends on "a", "with", ...); or, with
+        ``no_repeat_ngram=n``, v would complete an n-gram the hypothesis already contains (n = 1: any token
+        it emitted).  A forbidden candidate takes no part in the selection; a finished beam is carried
+        unchanged.  Nothing is renormalised: ``scores`` stay cumulative log-probabilities over the full
+        vocabulary, and a call whose constraints never bind returns the unconstrained call's bits.  Each
+        list holds at most 64 ids in ``[0, vocab)`` (duplicates allowed; ``end_id`` cannot be suppressed) and
+        is uploaded once per (device, ids) and cached; ``V - len(suppress_ids) - 1 - (max_len if
+        no_repeat_ngram else 0) >= beam_size`` must hold, so that a hypothesis always has K allowed
+        continuations, and ``no_repeat_ngram`` needs ``max_len <= 256``.  Constrained greedy decoding is
+        ``beam_size=1``."""
         import math
         K = int(beam_size)
         if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or int(groups) < 1:
@@ -559,6 +575,13 @@ class Encoder2Decoder(nn.Module):
             if isinstance(val, bool) or not (math.isfinite(f32[name]) and f32[name] >= 0.0):  # NaN fails
                 raise ValueError(f"{name} must be finite and >= 0 (as fp32), got {val!r}")
         plain = G == 1 and f32["diversity"] == 0.0 and f32["length_penalty"] == 0.0 and not return_details
+        constrained = not (type(suppress_ids) is tuple and not suppress_ids and type(no_end_after) is tuple
+                           and not no_end_after and type(min_length) is int and min_length == 0
+                           and type(no_repeat_ngram) is int and no_repeat_ngram == 0)
+        if constrained:  # (the defaults skip the validation: a decode loop's call stays as cheap as it was)
+            sup, nea, nmin, ngram = self._check_constraints(int(max_len), K, int(end_id), suppress_ids, min_length,
+                                                            no_repeat_ngram, no_end_after)
+            constrained = bool(sup or nea or nmin or ngram)
         check = False
         if exact_vocab is not None:
             if exact_vocab and fast:
@@ -590,15 +613,71 @@ class Encoder2Decoder(nn.Module):
                     (_lib.BEAM_FAST if fast else 0) | (_lib.DECODE_EXACT_VOCAB if check else 0),
                     _lib.stream_handle(),
                     vocab_events)
-            if plain:
+            opts = None
+            if not plain:
+                lens, ranks, grp = details or (None, None, None)
+                opts = ctypes.byref(_lib.BeamOpts(G, f32["diversity"], f32["length_penalty"], _lib.ptr(lens),
+                                                  _lib.ptr(ranks), _lib.ptr(grp)))
+            if constrained:
+                sup_dev, nea_dev = self._ids_on_device(dev, sup), self._ids_on_device(dev, nea)
+                cons = _lib.BeamConstraints(_lib.ptr(sup_dev), len(sup), nmin, ngram, _lib.ptr(nea_dev), len(nea))
+                rc = lib.aa_beam_decode_cx(*args, opts, ctypes.byref(cons))
+            elif plain:
                 rc = lib.aa_beam_decode(*args)
             else:
-                lens, ranks, grp = details or (None, None, None)
-                opts = _lib.BeamOpts(G, f32["diversity"], f32["length_penalty"], _lib.ptr(lens), _lib.ptr(ranks),
-                                     _lib.ptr(grp))
-                rc = lib.aa_beam_decode_ex(*args, ctypes.byref(opts))
+                rc = lib.aa_beam_decode_ex(*args, opts)
         _lib.check(rc, "beam_decode")
         return (ids, alpha, beta, seqs, scores) + details
+
+    def _check_constraints(self, T, K, end_id, suppress_ids, min_length, no_repeat_ngram, no_end_after):
+        """Validates ``beam_search``'s four constraint arguments (ValueError; no library call) ->
+        (suppress_ids tuple, no_end_after tuple, min_length, no_repeat_ngram)."""
+        V = self.dims.vocab
+        lists = {}
+        for name, ids in (("suppress_ids", suppress_ids), ("no_end_after", no_end_after)):
+            if isinstance(ids, torch.Tensor):
+                ids = ids.tolist()
+            try:
+                ids = tuple(ids)
+            except TypeError:
+                raise ValueError(f"{name} must be a sequence of token ids, got {ids!r}") from None
+            for v in ids:
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < V:
+                    raise ValueError(f"{name} must hold integer token ids in [0, {V}), got {v!r}")
+            if len(ids) > _lib.MAX_BEAM_SUPPRESS:
+                raise ValueError(f"{name} holds {len(ids)} ids, at most {_lib.MAX_BEAM_SUPPRESS} are supported")
+            lists[name] = tuple(int(v) for v in ids)
+        nums = {}
+        for name, val in (("min_length", min_length), ("no_repeat_ngram", no_repeat_ngram)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or int(val) < 0:
+                raise ValueError(f"{name} must be an integer >= 0, got {val!r}")
+            nums[name] = min(int(val), 2 ** 31 - 1)
+        sup, nea = lists["suppress_ids"], lists["no_end_after"]
+        if end_id in sup:
+            raise ValueError(f"suppress_ids must not hold end_id = {end_id}: use min_length to delay <end>")
+        if end_id < 0 and (nums["min_length"] > 0 or nea):
+            raise ValueError("min_length and no_end_after need an end_id >= 0")
+        if nums["no_repeat_ngram"] and T > _lib.MAX_BEAM_NGRAM_T:
+            raise ValueError(f"no_repeat_ngram needs max_len <= {_lib.MAX_BEAM_NGRAM_T}, got {T}")
+        if (sup or nea or nums["min_length"] or nums["no_repeat_ngram"]) and \
+                V - len(sup) - 1 - (T if nums["no_repeat_ngram"] else 0) < K:
+            raise ValueError(f"the constraints can leave a hypothesis fewer than beam_size = {K} allowed tokens: vocab "
+                             f"{V} - {len(sup)} suppressed - 1 - {T if nums['no_repeat_ngram'] else 0} (n-gram rule)")
+        return sup, nea, nums["min_length"], nums["no_repeat_ngram"]
+
+    def _ids_on_device(self, dev, ids):
+        """A tuple of token ids on ``dev`` as int32 (None when empty), uploaded once per (device, ids) and
+        cached, as ``_lengths_on_device`` does: a decode loop issues no pageable host->device copy per call."""
+        if not ids:
+            return None
+        cache = self.__dict__.setdefault("_ids_dev_cache", {})
+        key = (dev, ids)
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) > 64:
+                cache.clear()
+            hit = cache[key] = torch.tensor(ids, dtype=torch.int32, device=dev)
+        return hit
 
     @torch.no_grad()
     def sample(self, images: torch.Tensor, max_len: int = 20, temperature: float = 1.0, seed: int = 0,

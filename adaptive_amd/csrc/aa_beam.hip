@@ -24,6 +24,11 @@
 // aa_beam_decode_ex (diverse groups, length-normalised final ranking; semantics in adaptive_amd.h,
 // restated by tests/beam_div_oracle.py) runs the same step with k_beam_select3<true> and
 // k_beam_final_ex; aa_beam_decode keeps k_beam_select3<false> and k_beam_final.
+//
+// aa_beam_decode_cx (suppressed tokens, minimum length, no repeated n-grams, no <end> after given tokens;
+// semantics in adaptive_amd.h, restated by tests/beam_cons_oracle.py) swaps in k_beam_select3c<GROUPED> when a
+// constraint is set, and nothing else; aa_beam_select_step runs k_gsumm and one selection on caller-supplied
+// logits.
 #include "aa_internal.hpp"
 
 namespace aa {
@@ -571,20 +576,117 @@ __global__ __launch_bounds__(1024) void k_vbeam5(int R, int V, int Vp, const bf1
 // row's raw top K has K raw-better candidates in its row, at least Kg of them unpenalised, which beat
 // it on the augmented key as well (ties included: the tie order is the same q V + v).  Only the merge
 // differs: see below.  Kg and lam are read by the GROUPED instantiation alone.
-template <bool GROUPED>
-__global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int R, int t, int end_id,
-                                                      const float* __restrict__ logits,
-                                                      const float2* __restrict__ gsum, float* __restrict__ cum,
-                                                      int* __restrict__ fin, int64_t* __restrict__ tok,
-                                                      int* __restrict__ par, int* __restrict__ htok,
-                                                      int* __restrict__ hpar, int Kg, float lam) {
-  constexpr int GPL = 8;  // granule summaries held per lane: NG <= 512 (V <= 16384)
+//
+// CONS (constrained decode, aa_beam_decode_cx; k_beam_select3c): a live row's forbidden tokens F (rules 1-4
+// of adaptive_amd.h) are a bit per column in LDS, one 32-bit word per granule (cons_forbid).  M, S and so
+// the log-sum-exp come from the unmodified summaries: a survivor's score is the unconstrained expression on
+// the same operands, the same bits.  The threshold must not: a forbidden token that is its granule's max
+// would lift theta above granules that hold the row's best allowed tokens.  So every granule with a
+// non-zero word has its max recomputed over its allowed columns from the logits (a_g; -inf if none is
+// left, which drops the granule like an empty one), a_g = m_g elsewhere, and theta is the K-th largest
+// a_g.  Exact: each of the K granules with the largest a_g holds an allowed token >= theta, so K allowed
+// tokens reach theta (with fewer than K such granules every one of them is a candidate, as in the plain
+// kernel); an allowed token of a granule with a_g < theta is below theta itself, strictly below K allowed
+// tokens, and cannot be among the row's K best whatever the tie order.  The candidate scan gives forbidden
+// columns key 0, which no round selects.  Every live row has K allowed columns (the entry points refuse
+// V - |suppress| - 1 - T < K), so no round runs dry.  The GROUPED argument above then holds with "candidate"
+// read as "allowed candidate": the penalty still touches at most K - Kg tokens.  A finished row builds no
+// F: its carried <end> enters the merge as before.  The merge is unchanged.
+constexpr int BEAM_GPL = 8;  // granule summaries held per lane: NG <= 512 (V <= 16384)
+
+struct BeamCons {  // aa_beam_constraints as the kernel takes it (ids: device memory)
+  const int* sup;
+  const int* nea;
+  int nsup, nnea, min_len, ngram;
+};
+
+__device__ __forceinline__ uint32_t* cons_mask() {  // [BEAM_MAX][64 BEAM_GPL]: a row's forbidden columns
+  __shared__ uint32_t s_mask[BEAM_MAX * 64 * BEAM_GPL];
+  return s_mask;
+}
+// dynamic LDS of the n-gram rule (2 t K ints): the image's history [t][K] as tok | parent slot << 16, then
+// the K rows' own tokens [K][t]
+__device__ __forceinline__ int* cons_hist() {
+  extern __shared__ int s_hist[];
+  return s_hist;
+}
+
+// Builds live row `row`'s forbidden-column bits in fm (one wave).  An id outside [0, V) sets nothing.
+__device__ __forceinline__ void cons_forbid(uint32_t* fm, const BeamCons& cn, int K, int V, int R, int t, int end_id,
+                                            int b, int k, int row, int lane, const int* __restrict__ htok) {
+#pragma unroll
+  for (int i = 0; i < BEAM_GPL; ++i) fm[lane + 64 * i] = 0u;
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  auto forbid = [&](int v) {
+    if (v >= 0 && v < V) atomicOr(&fm[v >> 5], 1u << (v & 31));
+  };
+  // rule 1 (end_id is never suppressed: the entry points refuse it where they can see the ids)
+  if (lane < cn.nsup) {
+    const int v = cn.sup[lane];
+    if (v != end_id) forbid(v);
+  }
+  // rules 2 and 3: <end> before min_length, or right after a token of no_end_after (y_{-1} = <start> = 1)
+  if (end_id >= 0) {
+    bool ban = t < cn.min_len;
+    if (cn.nnea > 0) {
+      const int last = t ? htok[(int64_t)(t - 1) * R + row] : 1;
+      ban = ban || __ballot(lane < cn.nnea && cn.nea[lane] == last) != 0;
+    }
+    if (ban && lane == 0) forbid(end_id);
+  }
+  // rule 4: lane 0 walks the row's own tokens y_0 .. y_{t-1} out of the staged history (LDS pointer
+  // chasing, t steps), then lane j tests whether the n-gram ending at y_j starts like the one v would end
+  const int n = cn.ngram;
+  if (n > 0 && t >= n) {
+    const int* hist = cons_hist();
+    int* y = cons_hist() + t * K + k * t;
+    if (lane == 0) {
+      int j = k;
+      for (int s = t - 1; s >= 0; --s) {
+        const int e = hist[s * K + j];
+        y[s] = e & 0xFFFF;
+        j = min((e >> 16) & 7, K - 1);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int j = n - 1 + lane; j < t; j += 64) {
+      bool eq = true;
+      for (int i = 1; i < n; ++i) eq = eq && y[j - i] == y[t - i];
+      if (eq) forbid(y[j]);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
+template <bool GROUPED, bool CONS>
+__device__ __forceinline__ void beam_select3(int K, int V, int Vp, int R, int t, int end_id,
+                                             const float* __restrict__ logits, const float2* __restrict__ gsum,
+                                             float* __restrict__ cum, int* __restrict__ fin,
+                                             int64_t* __restrict__ tok, int* __restrict__ par,
+                                             int* __restrict__ htok, int* __restrict__ hpar, int Kg, float lam,
+                                             const BeamCons& cn) {
+  constexpr int GPL = BEAM_GPL;
   __shared__ float s_mx[BEAM_MAX], s_ls[BEAM_MAX];
   __shared__ uint64_t s_top[BEAM_MAX][BEAM_MAX];
   __shared__ int s_cand[BEAM_MAX][64 * GPL];
   const int b = blockIdx.x, lane = threadIdx.x & 63, k = threadIdx.x >> 6;
   const int NG = Vp / 32;
   const int row = b * K + k;
+  if constexpr (CONS) {
+    // the n-gram rule reads the image's step history: staged once per workgroup, before any wave leaves
+    if (cn.ngram > 0 && t >= cn.ngram) {
+      int* hist = cons_hist();
+      for (int i = threadIdx.x; i < t * K; i += 64 * K) {
+        const int s = i / K, j = i - s * K;
+        const int64_t o = (int64_t)s * R + b * K + j;
+        hist[i] = (htok[o] & 0xFFFF) | (hpar[o] << 16);
+      }
+      __syncthreads();
+    }
+  }
   const bool live = !(t == 0 && (GROUPED ? k % Kg != 0 : k > 0)) && fin[row] == 0;  // uniform over the wave
   if (live) {
     const float2* gs = gsum + (int64_t)row * NG;
@@ -605,6 +707,32 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
     for (int i = 0; i < GPL; ++i)
       if (gm[i] != -INFINITY) S += gv[i] * expf(gm[i] - M);
     S = wave_sum(S);
+    [[maybe_unused]] uint32_t* fm = nullptr;
+    if constexpr (CONS) {
+      fm = cons_mask() + k * (64 * GPL);
+      cons_forbid(fm, cn, K, V, R, t, end_id, b, k, row, lane, htok);
+      // a_g of the granules that hold a forbidden column, from the logits themselves; M and S above are the
+      // unconstrained row's and stay
+      const float4* xg = reinterpret_cast<const float4*>(logits + (int64_t)row * Vp);
+#pragma unroll
+      for (int i = 0; i < GPL; ++i) {
+        const int g = lane + 64 * i;
+        const uint32_t fb = g < NG ? fm[g] : 0u;
+        if (fb != 0u) {
+          float a = -INFINITY;
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const float4 v = xg[g * 8 + q];
+            const int c = g * 32 + 4 * q;
+            if (!((fb >> (4 * q)) & 1u) && c < V) a = fmaxf(a, v.x);
+            if (!((fb >> (4 * q + 1)) & 1u) && c + 1 < V) a = fmaxf(a, v.y);
+            if (!((fb >> (4 * q + 2)) & 1u) && c + 2 < V) a = fmaxf(a, v.z);
+            if (!((fb >> (4 * q + 3)) & 1u) && c + 3 < V) a = fmaxf(a, v.w);
+          }
+          gm[i] = a;
+        }
+      }
+    }
     // K-th largest granule max (by value, then lower granule first); a row with fewer than K
     // non-empty granules (V <= 32 (K - 1)) runs out of them (best == 0) and keeps the last one found,
     // its smallest granule max, so every non-empty granule is a candidate.  A live row has at least
@@ -640,7 +768,8 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
       uint64_t best = 0;
       for (int e = lane; e < n * 32; e += 64) {
         const int c = s_cand[k][e >> 5] * 32 + (e & 31);
-        const uint64_t key = c < V ? argmax_key(x[c], c) : 0ull;
+        uint64_t key = c < V ? argmax_key(x[c], c) : 0ull;
+        if constexpr (CONS) key = ((fm[c >> 5] >> (c & 31)) & 1u) ? 0ull : key;
         if (key < prev && key > best) best = key;
       }
       best = wave_max_u64(best);
@@ -727,6 +856,30 @@ __global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int 
   }
 }
 
+template <bool GROUPED>
+__global__ __launch_bounds__(512) void k_beam_select3(int K, int V, int Vp, int R, int t, int end_id,
+                                                      const float* __restrict__ logits,
+                                                      const float2* __restrict__ gsum, float* __restrict__ cum,
+                                                      int* __restrict__ fin, int64_t* __restrict__ tok,
+                                                      int* __restrict__ par, int* __restrict__ htok,
+                                                      int* __restrict__ hpar, int Kg, float lam) {
+  beam_select3<GROUPED, false>(K, V, Vp, R, t, end_id, logits, gsum, cum, fin, tok, par, htok, hpar, Kg, lam,
+                               BeamCons{});
+}
+// the constrained selection: launched with cons_lds(cn, K, t) bytes of dynamic LDS
+template <bool GROUPED>
+__global__ __launch_bounds__(512) void k_beam_select3c(int K, int V, int Vp, int R, int t, int end_id,
+                                                       const float* __restrict__ logits,
+                                                       const float2* __restrict__ gsum, float* __restrict__ cum,
+                                                       int* __restrict__ fin, int64_t* __restrict__ tok,
+                                                       int* __restrict__ par, int* __restrict__ htok,
+                                                       int* __restrict__ hpar, int Kg, float lam, BeamCons cn) {
+  beam_select3<GROUPED, true>(K, V, Vp, R, t, end_id, logits, gsum, cum, fin, tok, par, htok, hpar, Kg, lam, cn);
+}
+static size_t cons_lds(const BeamCons& cn, int K, int t) {
+  return (cn.ngram > 0 && t >= cn.ngram) ? sizeof(int) * 2 * (size_t)t * K : 0;
+}
+
 struct BeamWS {
   EncWS e;  // of the B images (+ xg1: their x_g, expanded to the rows' r.xg)
   RowWS r;  // of the R = B K rows
@@ -785,6 +938,50 @@ static int beam_check(const aa_dims* d, int B, int T, int K) {
   return AA_OK;
 }
 
+// The constraints' argument checks, made before the B == 0 / T == 0 return (T: the steps whose tokens the
+// n-gram rule can see).  *cn: what the kernel takes; *on: a constraint is set (else the unconstrained
+// kernels run).  The ids themselves are device memory: the kernel ignores one outside [0, V).
+static int cons_check(const aa_beam_constraints* c, int V, int T, int K, int end_id, BeamCons* cn, bool* on) {
+  *cn = BeamCons{};
+  *on = false;
+  if (!c) return AA_OK;
+  if (c->n_suppress < 0 || c->n_suppress > AA_MAX_BEAM_SUPPRESS) return AA_ERR_SHAPE;
+  if (c->n_no_end_after < 0 || c->n_no_end_after > AA_MAX_BEAM_SUPPRESS) return AA_ERR_SHAPE;
+  if (c->min_length < 0 || c->no_repeat_ngram < 0) return AA_ERR_SHAPE;
+  if ((c->min_length > 0 || c->n_no_end_after > 0) && end_id < 0) return AA_ERR_SHAPE;
+  if (c->no_repeat_ngram > 0 && T > AA_MAX_BEAM_NGRAM_T) return AA_ERR_SHAPE;
+  // every live row keeps K allowed candidates: the selection cannot run dry
+  if ((int64_t)V - c->n_suppress - 1 - (c->no_repeat_ngram > 0 ? T : 0) < K) return AA_ERR_SHAPE;
+  *cn = BeamCons{c->suppress_ids, c->no_end_after, c->n_suppress, c->n_no_end_after, c->min_length, c->no_repeat_ngram};
+  *on = c->n_suppress > 0 || c->n_no_end_after > 0 || c->min_length > 0 || c->no_repeat_ngram > 0;
+  return AA_OK;
+}
+static bool cons_null(const BeamCons& cn) { return (cn.nsup > 0 && !cn.sup) || (cn.nnea > 0 && !cn.nea); }
+
+// one step's selection launch: the four unconstrained / constrained, plain / grouped kernels
+static void select_launch(int B, int K, int V, int Vp, int R, int t, int end_id, const float* logits,
+                          const float2* gsum, float* cum, int* fin, int64_t* tok, int* par, int* htok, int* hpar,
+                          const aa_beam_opts* opts, bool con, const BeamCons& cn, hipStream_t s) {
+  const int Kg = opts ? K / opts->groups : 0;
+  const float lam = opts ? opts->diversity : 0.f;
+  const int e = end_id < 0 ? -1 : end_id;
+  if (con) {
+    const size_t lds = cons_lds(cn, K, t);
+    if (opts)
+      hipLaunchKernelGGL(k_beam_select3c<true>, dim3(B), dim3(64 * K), lds, s, K, V, Vp, R, t, e, logits, gsum, cum,
+                         fin, tok, par, htok, hpar, Kg, lam, cn);
+    else
+      hipLaunchKernelGGL(k_beam_select3c<false>, dim3(B), dim3(64 * K), lds, s, K, V, Vp, R, t, e, logits, gsum, cum,
+                         fin, tok, par, htok, hpar, 0, 0.f, cn);
+  } else if (opts) {
+    hipLaunchKernelGGL(k_beam_select3<true>, dim3(B), dim3(64 * K), 0, s, K, V, Vp, R, t, e, logits, gsum, cum, fin,
+                       tok, par, htok, hpar, Kg, lam);
+  } else {
+    hipLaunchKernelGGL(k_beam_select3<false>, dim3(B), dim3(64 * K), 0, s, K, V, Vp, R, t, e, logits, gsum, cum, fin,
+                       tok, par, htok, hpar, 0, 0.f);
+  }
+}
+
 }  // namespace aa
 
 using namespace aa;
@@ -796,11 +993,12 @@ size_t aa_beam_workspace_bytes(const aa_dims* d, int32_t B, int32_t T, int32_t K
   return n;
 }
 
-// aa_beam_decode (opts == nullptr: the plain selection and final kernels) and aa_beam_decode_ex
+// aa_beam_decode (opts == nullptr: the plain selection and final kernels), aa_beam_decode_ex and
+// aa_beam_decode_cx (a constraint set: the constrained selection)
 static int beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
                        int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
                        size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events,
-                       const aa_beam_opts* opts) {
+                       const aa_beam_opts* opts, const aa_beam_constraints* cons) {
   Layout L;
   int rc = check_model(m, &L);
   if (rc) return rc;
@@ -814,8 +1012,12 @@ static int beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t
     if (!(opts->length_penalty >= 0.f) || !(opts->length_penalty <= 3.402823466e38f)) return AA_ERR_SHAPE;
   }
   const int Kg = opts ? K / opts->groups : K;
+  BeamCons cn;
+  bool con;
+  rc = cons_check(cons, L.V, T, K, end_id, &cn, &con);
+  if (rc) return rc;
   if (B == 0 || T == 0) return AA_OK;
-  if (!feats || !workspace) return AA_ERR_NULL;
+  if (!feats || !workspace || cons_null(cn)) return AA_ERR_NULL;
   if (!al16(feats) || !al16(workspace)) return AA_ERR_ALIGN;
   size_t need;
   BeamWS w = carve_beam(static_cast<char*>(workspace), L, B, T, K, &need);
@@ -841,14 +1043,7 @@ static int beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t
   AA_TRY(hipMemsetAsync(w.cum, 0, sizeof(float) * R, s));
   AA_TRY(hipMemsetAsync(w.fin, 0, sizeof(int) * R, s));
   auto select = [&](int t) {
-    if (opts)
-      hipLaunchKernelGGL(k_beam_select3<true>, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t,
-                         end_id < 0 ? -1 : end_id, w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar, Kg,
-                         opts->diversity);
-    else
-      hipLaunchKernelGGL(k_beam_select3<false>, dim3(B), dim3(64 * K), 0, s, K, L.V, L.Vp, R, t,
-                         end_id < 0 ? -1 : end_id, w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar, 0,
-                         0.f);
+    select_launch(B, K, L.V, L.Vp, R, t, end_id, w.logits, w.gsum, w.cum, w.fin, w.tok, w.par, w.htok, w.hpar, opts, con, cn, s);
   };
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
@@ -899,7 +1094,7 @@ int aa_beam_decode(const aa_model* m, const float* feats, int32_t B, int32_t T, 
                    int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
                    size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events) {
   return beam_decode(m, feats, B, T, K, end_id, ids, seqs, scores, alpha, beta, workspace, workspace_bytes, flags,
-                     stream, vocab_events, nullptr);
+                     stream, vocab_events, nullptr, nullptr);
 }
 
 int aa_beam_decode_ex(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
@@ -907,5 +1102,80 @@ int aa_beam_decode_ex(const aa_model* m, const float* feats, int32_t B, int32_t 
                       size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events,
                       const aa_beam_opts* opts) {
   return beam_decode(m, feats, B, T, K, end_id, ids, seqs, scores, alpha, beta, workspace, workspace_bytes, flags,
-                     stream, vocab_events, opts);
+                     stream, vocab_events, opts, nullptr);
+}
+
+int aa_beam_decode_cx(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K, int32_t end_id,
+                      int64_t* ids, int64_t* seqs, float* scores, float* alpha, float* beta, void* workspace,
+                      size_t workspace_bytes, int32_t flags, aa_stream_t stream, aa_event_t* vocab_events,
+                      const aa_beam_opts* opts, const aa_beam_constraints* cons) {
+  return beam_decode(m, feats, B, T, K, end_id, ids, seqs, scores, alpha, beta, workspace, workspace_bytes, flags,
+                     stream, vocab_events, opts, cons);
+}
+
+// ---- one step's selection on caller-supplied logits -------------------------------------------------
+namespace {
+struct StepWS {
+  float2* gsum;
+  int *htok, *hpar;
+};
+StepWS carve_step(char* base, int R, int Vp, int t, size_t* bytes) {
+  Carver c{base};
+  StepWS w;
+  w.gsum = c.take<float2>((size_t)R * (Vp / 32));
+  w.htok = c.take<int>((size_t)(t + 1) * R);
+  w.hpar = c.take<int>((size_t)(t + 1) * R);
+  *bytes = c.off;
+  return w;
+}
+int step_check(int B, int K, int V, int Vp, int t) {
+  if (B < 0 || K < 1 || K > BEAM_MAX || (int64_t)B * K > (int64_t)1 << 24) return AA_ERR_SHAPE;
+  if (V < 1 || V > 64 * 32 * BEAM_GPL || K > V || Vp < V || Vp % 32 != 0 || Vp > 64 * 32 * BEAM_GPL) return AA_ERR_SHAPE;
+  if (t < 0 || t > (1 << 20)) return AA_ERR_SHAPE;
+  return AA_OK;
+}
+}  // namespace
+
+size_t aa_beam_select_step_workspace_bytes(int32_t B, int32_t K, int32_t V, int32_t Vp, int32_t t) {
+  if (step_check(B, K, V, Vp, t) != AA_OK) return 0;
+  size_t n;
+  carve_step(nullptr, B * K, Vp, t, &n);
+  return n;
+}
+
+int aa_beam_select_step(int32_t B, int32_t K, int32_t V, int32_t Vp, int32_t t, int32_t end_id, const float* logits,
+                        const float* cum, const int32_t* fin, const int32_t* hist_tok, const int32_t* hist_par,
+                        const aa_beam_opts* opts, const aa_beam_constraints* cons, int64_t* tok, int32_t* par,
+                        float* cum_out, int32_t* fin_out, void* workspace, size_t workspace_bytes,
+                        aa_stream_t stream) {
+  int rc = step_check(B, K, V, Vp, t);
+  if (rc) return rc;
+  if (end_id >= V) return AA_ERR_SHAPE;
+  if (opts) {
+    if (opts->groups < 1 || K % opts->groups != 0) return AA_ERR_SHAPE;
+    if (!(opts->diversity >= 0.f) || !(opts->diversity <= 3.402823466e38f)) return AA_ERR_SHAPE;
+  }
+  BeamCons cn;
+  bool con;
+  rc = cons_check(cons, V, t, K, end_id, &cn, &con);
+  if (rc) return rc;
+  if (B == 0) return AA_OK;
+  if (!logits || !cum || !fin || !tok || !par || !cum_out || !fin_out || !workspace || cons_null(cn)) return AA_ERR_NULL;
+  if (t > 0 && (!hist_tok || !hist_par)) return AA_ERR_NULL;
+  if (!al16(logits) || !al16(workspace)) return AA_ERR_ALIGN;
+  const int R = B * K;
+  size_t need;
+  StepWS w = carve_step(static_cast<char*>(workspace), R, Vp, t, &need);
+  if (workspace_bytes < need) return AA_ERR_BUFFER;
+  hipStream_t s = (hipStream_t)stream;
+  if (t > 0) {
+    AA_TRY(hipMemcpyAsync(w.htok, hist_tok, sizeof(int) * (size_t)t * R, hipMemcpyDeviceToDevice, s));
+    AA_TRY(hipMemcpyAsync(w.hpar, hist_par, sizeof(int) * (size_t)t * R, hipMemcpyDeviceToDevice, s));
+  }
+  if (cum_out != cum) AA_TRY(hipMemcpyAsync(cum_out, cum, sizeof(float) * R, hipMemcpyDeviceToDevice, s));
+  if (fin_out != fin) AA_TRY(hipMemcpyAsync(fin_out, fin, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(k_gsumm, dim3((unsigned)((((R + 31) / 32) * (Vp / 32) + 3) / 4)), dim3(256), 0, s, R, V, Vp, logits,
+                     w.gsum);
+  select_launch(B, K, V, Vp, R, t, end_id, logits, w.gsum, cum_out, fin_out, tok, par, w.htok, w.hpar, opts, con, cn, s);
+  return launch_status();
 }

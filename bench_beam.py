@@ -13,6 +13,12 @@ sample on this host.
 decode (aa_beam_decode_ex: k_beam_select3<true>, k_beam_final_ex), and its "ab" entry compares it with the
 plain call (aa_beam_decode) at the same beam width in this process: --regions alternating regions of
 --steps calls each, the median region of either, and their ratio.
+
+--suppress N / --min-length M / --no-repeat-ngram n / --no-end-after N (any of them given): the line is that
+of the constrained decode (aa_beam_decode_cx: k_beam_select3c) with the other options as given, and its "cons"
+entry compares it with the same call without constraints in this process, as "ab" does.  The suppressed ids
+are the N most frequent non-<end> tokens of a warm-up decode, the no-end-after ids the most frequent ones
+after those.
 """
 from __future__ import annotations
 
@@ -71,7 +77,12 @@ def main():
     ap.add_argument("--groups", type=int, default=None, help="diverse beam search: G groups of beam / G slots")
     ap.add_argument("--diversity", type=float, default=None, help="Hamming diversity penalty per earlier group's pick")
     ap.add_argument("--length-penalty", type=float, default=None, help="rank the final beams by score / len^A")
-    ap.add_argument("--regions", type=int, default=5, help="grouped decode: alternating regions per side of the A/B")
+    ap.add_argument("--regions", type=int, default=5, help="grouped / constrained decode: alternating regions per "
+                    "side of the A/B")
+    ap.add_argument("--suppress", type=int, default=0, help="suppress the N most frequent tokens of a warm-up decode")
+    ap.add_argument("--min-length", type=int, default=0, help="no <end> before this many tokens")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, help="no n-gram twice in a hypothesis")
+    ap.add_argument("--no-end-after", type=int, default=0, help="no <end> right after the next N most frequent tokens")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, K, T = args.batch, args.beam, args.T
@@ -93,8 +104,31 @@ def main():
     for _ in range(args.warmup):
         model.beam_search(feats, T, K, fast=args.fast, **div)
     el, out = region(div)
-    ab = None
-    if grouped:
+    ab = cons = None
+    if args.suppress or args.min_length or args.no_repeat_ngram or args.no_end_after:
+        seqs = out[3].flatten()
+        ids, counts = torch.unique(seqs[seqs != 2], return_counts=True)
+        freq = ids[torch.argsort(counts, descending=True, stable=True)].tolist()
+        ckw = {"suppress_ids": tuple(freq[:args.suppress]), "min_length": args.min_length,
+               "no_repeat_ngram": args.no_repeat_ngram,
+               "no_end_after": tuple(freq[args.suppress:args.suppress + args.no_end_after])}
+        for _ in range(args.warmup):
+            out = model.beam_search(feats, T, K, fast=args.fast, **div, **ckw)
+        free_s, cons_s = [], []
+        for _ in range(max(1, args.regions)):
+            free_s.append(region(div)[0])
+            cons_s.append(region({**div, **ckw})[0])
+        mf, mc = float(np.median(free_s)), float(np.median(cons_s))
+        sel = "k_beam_select3c<true>" if grouped else "k_beam_select3c<false>"
+        cons = {"regions": len(cons_s), "calls_per_region": args.steps, **ckw,
+                "unconstrained": {"ms_per_call": 1e3 * mf / args.steps, "captions_per_s": B * args.steps / mf,
+                                  "region_ms": [1e3 * x for x in free_s]},
+                "constrained": {"path": f"aa_beam_decode_cx ({sel})", "ms_per_call": 1e3 * mc / args.steps,
+                                "captions_per_s": B * args.steps / mc, "region_ms": [1e3 * x for x in cons_s]},
+                "constrained_over_unconstrained_time": mc / mf}
+        div = {**div, **ckw}
+        el = mc
+    if grouped and not cons:
         for _ in range(args.warmup):
             model.beam_search(feats, T, K, fast=args.fast)
         plain_s, div_s = [], []
@@ -148,6 +182,8 @@ def main():
            "best_score_mean": float(out[4][:, 0].mean().item()), "roofline": roofline, "cpu_baseline": None}
     if ab:
         res["ab"] = ab
+    if cons:
+        res["cons"] = cons
     if not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(K, T, args.cpu_sample, args.cpu_budget)
         res["speedup_vs_cpu"] = res["value"] / res["cpu_baseline"]["value"]

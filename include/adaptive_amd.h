@@ -394,6 +394,76 @@ AA_API int aa_beam_decode_ex(const aa_model* m, const float* feats, int32_t B, i
                              float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
                              aa_stream_t stream, aa_event_t* vocab_events, const aa_beam_opts* opts);
 
+/* ---- constrained beam search: suppressed tokens, minimum length, no repeated n-grams ------------
+ * Additions to the beam decode; aa_beam_decode and aa_beam_decode_ex keep their signatures and
+ * behaviour.  Semantics defined here and in tests/beam_cons_oracle.py.  Take a live (unfinished)
+ * hypothesis at step t with its own tokens y_0 .. y_{t-1} (traced through its parents; <start> is not
+ * among them) and y_{-1} = 1 (<start>).  Candidate token v is forbidden iff
+ *   1. v is in suppress_ids;
+ *   2. v == end_id and t < min_length (a caption has min_length tokens before <end>; with
+ *      min_length >= T no beam finishes);
+ *   3. v == end_id and y_{t-1} is in no_end_after (no <end> right after "a", "the", "with", ...);
+ *   4. n = no_repeat_ngram >= 1 and some j in [n-1, t-1] has (y_{j-n+1} .. y_{j-1}) ==
+ *      (y_{t-n+1} .. y_{t-1}) and v == y_j: v would complete an n-gram the hypothesis already
+ *      contains (n = 1: any token it emitted).  A live hypothesis holds no end_id, so rule 4 never
+ *      forbids end_id.
+ * A forbidden candidate takes no part in the selection.  Everything else is aa_beam_decode_ex's: a
+ * finished beam keeps its single carried end_id at its unchanged score (no constraint applies to it);
+ * step-0 liveness, the groups' order under raw - diversity * n[v], the tie order and the final
+ * ranking are unchanged.  No renormalisation: a surviving candidate's score is the parent's score +
+ * log_softmax over the full vocabulary -- the same fp32 expression on the same logits and the same
+ * log-sum-exp from the same granule summaries -- so scores stay the model's log-probabilities, and a
+ * call whose constraints never bind returns the unconstrained call's bits.  Sampling, the greedy
+ * decode, renormalised and forced-word constraints are out of scope (constrained greedy is K = 1).
+ * The id arrays are device memory, int32, with duplicates allowed.  cons == NULL, or all four off, is
+ * aa_beam_decode_ex (opts == NULL as well: aa_beam_decode): the same kernels, the same bits.  The
+ * workspace is aa_beam_workspace_bytes'.
+ * Checks: as aa_beam_decode_ex, and before the B == 0 / T == 0 return AA_ERR_SHAPE for a list count
+ * outside [0, AA_MAX_BEAM_SUPPRESS], min_length < 0, no_repeat_ngram < 0, min_length > 0 or a
+ * non-empty no_end_after with end_id < 0, no_repeat_ngram > 0 with T > AA_MAX_BEAM_NGRAM_T (the rows'
+ * histories are staged in LDS), and V - n_suppress - 1 - (no_repeat_ngram ? T : 0) < K (every live
+ * row keeps K allowed candidates: the selection never runs dry).  A NULL list with a count > 0 is
+ * AA_ERR_NULL, with the other pointers.  The ids themselves cannot be checked without reading
+ * device memory: the caller keeps them inside [0, vocab) and end_id out of suppress_ids
+ * (Encoder2Decoder.beam_search raises ValueError); the kernel ignores an id outside [0, vocab) and
+ * an end_id among suppress_ids. */
+#define AA_MAX_BEAM_SUPPRESS 64
+#define AA_MAX_BEAM_NGRAM_T 256
+typedef struct aa_beam_constraints {
+  const int32_t* suppress_ids; /* [n_suppress], device memory */
+  int32_t n_suppress;
+  int32_t min_length;      /* 0: off */
+  int32_t no_repeat_ngram; /* 0: off */
+  const int32_t* no_end_after; /* [n_no_end_after], device memory */
+  int32_t n_no_end_after;
+} aa_beam_constraints;
+AA_API int aa_beam_decode_cx(const aa_model* m, const float* feats, int32_t B, int32_t T, int32_t K,
+                             int32_t end_id, int64_t* ids, int64_t* seqs, float* scores, float* alpha,
+                             float* beta, void* workspace, size_t workspace_bytes, int32_t flags,
+                             aa_stream_t stream, aa_event_t* vocab_events, const aa_beam_opts* opts,
+                             const aa_beam_constraints* cons);
+
+/* One step's selection on caller-supplied logits [R, Vp] fp32, R = B K rows (row b K + k is slot k of
+ * image b; columns V .. Vp - 1 take no part): the selection apart from the model, as aa_sample_select
+ * is for sampling.  The rows are at step t of a decode: cum [R] and fin [R] int32 are their scores and
+ * finished flags, hist_tok / hist_par [t, R] int32 the tokens and parent slots (0 .. K - 1) of steps
+ * 0 .. t - 1 as the decode keeps them (may be NULL when t == 0).  Computes the granule summaries
+ * (k_gsumm), then runs the step's selection kernel once -- the one aa_beam_decode (opts == NULL),
+ * aa_beam_decode_ex or, with a constraint set, aa_beam_decode_cx launches -- and writes tok [R] int64,
+ * par [R] int32 (the parent's row b K + q), cum_out [R] and fin_out [R] (each may alias its input).
+ * opts: groups and diversity are read.
+ * Checks: AA_ERR_SHAPE for B < 0, K outside [1, AA_MAX_BEAM], B K > 2^24, V outside [1, 16384], K > V,
+ * Vp < V, Vp % 32 != 0 or Vp > 16384, t outside [0, 2^20], end_id >= V, the options as aa_beam_decode_ex and the
+ * constraints as aa_beam_decode_cx with t in place of T; B == 0 returns AA_OK; then NULL pointers,
+ * AA_ERR_ALIGN unless logits and workspace are 16-byte aligned, AA_ERR_BUFFER below
+ * aa_beam_select_step_workspace_bytes (0 for arguments the call refuses). */
+AA_API size_t aa_beam_select_step_workspace_bytes(int32_t B, int32_t K, int32_t V, int32_t Vp, int32_t t);
+AA_API int aa_beam_select_step(int32_t B, int32_t K, int32_t V, int32_t Vp, int32_t t, int32_t end_id,
+                               const float* logits, const float* cum, const int32_t* fin,
+                               const int32_t* hist_tok, const int32_t* hist_par, const aa_beam_opts* opts,
+                               const aa_beam_constraints* cons, int64_t* tok, int32_t* par, float* cum_out,
+                               int32_t* fin_out, void* workspace, size_t workspace_bytes, aa_stream_t stream);
+
 /* ---- seeded temperature-sampling decode ---------------------------------------------------------
  * Not in the reference: semantics defined here and in tests/sample_oracle.py SampleOracle.  One
  * caption per image drawn from the model's own distribution by Gumbel-max over the exact fp32 logits
